@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""bench.py - batched SBROS-v1 env-steps/s on N MI355X (one process per GPU), next to the kernel's roofline and a
-CPU baseline.
+"""bench.py - batched SBROS-v1 env-steps/s on N MI355X (one process per GPU), next to the kernel's roofline and (with `--full`)
+a CPU baseline.
 
-    python bench.py --gpus 1 --steps K --warmup W                         (N = 1)
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]      (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W                            (N > 1, RCCL)
 
@@ -44,7 +44,14 @@ untimed to call 36, five warm-up calls follow, and calls 41 .. 60 are timed - te
 phase-boundary call with its double step, nine aerobic ones (`config.timed_calls`, `config.anoxic_share_of_timed_calls`).  Until
 round 5 the region was calls 5 .. 24, all anoxic: the cheapest twenty calls of an episode.  Regions of an episode or more start at
 call W as before (they hold every kind of call, the terminal call and the reset).
-The large-batch leg.  With `--gpus 1`, workload config2 and no `--envs-per-gpu`, the run then times a SECOND handle of 262 144 envs
+A plain run (no `--full`) sets up, warms up, times the K steps, writes the outputs of the last timed step if `--dump-outputs DIR`
+is given, and prints the line.  Everything else the bench measures runs only under `--full`, after the timed region: the
+large-batch leg, the device-counted Butcher-5 step statistics (`fp64_valu.b5_steps_per_interval`, one more untimed episode) and the
+CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned to its caller, one DIR/<name>.npy per array in
+float32 or float64 (rank 0's shard when N > 1; at most 64 MB, else a fixed seeded sample of envs): sbr_step's obs, state,
+reward, done; the fused rollout's per-env reward sums; the per-cycle env's obs, reward, done.  The timed episode's reset seed
+does not depend on how many episodes the clock priming took, so the same arguments give the same outputs from run to run.
+The large-batch leg.  With `--full`, `--gpus 1`, workload config2 and no `--envs-per-gpu`, the run then times a SECOND handle of 262 144 envs
 (configs[3]'s total on one GPU, 84 MB of state; above 65 536 envs a launch has more wavefronts than the chip has SIMDs and runs the
 two-waves-per-SIMD build of k_step) with the same bracket, priming, window and K, and reports it as
 `roofline.larger_batches["262144"]` with `measured_in_this_run: true`: north_star's ">= 40 % of HBM roofline on one MI355X" measured
@@ -96,6 +103,7 @@ MAX_CLOCK_GHZ = 2.4                    # the same guide, chip-level parameters
 SIMDS = 1024
 PRIME_SECONDS = 0.3                    # untimed: brings the GPU to steady clocks before warm-up and timing
 LARGE_LEG_ENVS = 262144                # the in-run large-batch leg: configs[3]'s total on ONE GPU (k_step's two-waves-per-SIMD build)
+DUMP_MAX_BYTES = 60 * 10**6            # --dump-outputs: at most 64 MB in all, .npy headers included; above it a seeded sample of envs
 
 
 def episode_schedule(cfg=None):
@@ -314,6 +322,30 @@ def loaded_library_hash():
         return None
 
 
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: write `arrays` (name -> tensor or array, env index first) as out_dir/<name>.npy.  Floating arrays keep
+    their precision; flags and integers become float32 / float64 (exact).  When the whole set exceeds `max_bytes`, the same
+    seeded sample of env rows is taken from every array and its indices go to out_dir/sample_env_index.npy."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        host[name] = a
+    n = min(a.shape[0] for a in host.values())
+    total = sum(a.nbytes for a in host.values())
+    if total > max_bytes:
+        keep = max(1, int(n * max_bytes / (total + 8.0 * n)))          # the index array counts too
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        host = {name: np.ascontiguousarray(a[idx]) for name, a in host.items()}
+        host["sample_env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(host)
+
+
 INTERVALS_PER_CYCLE = 528      # 24 + 48 + 223 + 186 + 11 + 36 control intervals (tests/golden/sbrv2_cycles.npz)
 FILL_INTERVALS = 24            # the first phase integrates the filling right-hand side
 
@@ -331,7 +363,7 @@ def bench_cycle(args, torch, dist, world, rank, local_rank, dev, emit):
     scenario = ((torch.arange(n_local, device=dev) + rank * n_local) % 8).to(torch.int32)
     gen = torch.Generator(device=dev); gen.manual_seed(4321 + rank)
     pool = torch.rand(16, n_local, 3, device=dev, generator=gen)
-    steps = max(1, min(args.steps, 64)) if args.steps == 1852 else args.steps       # default K is sized for config2
+    steps = args.steps
 
     def one(k):
         env.reset(seed=k, scenario=scenario)
@@ -357,6 +389,8 @@ def bench_cycle(args, torch, dist, world, rank, local_rank, dev, emit):
     e1.record(); torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0          # clock read between the closing synchronise and the closing barrier, see main()
     fence()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"obs": env.cobs, "reward": env.reward, "done": env.all_done})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX); elapsed = float(t.item())
@@ -437,7 +471,8 @@ class StepLeg:
             pool = torch.rand(64, n_local, 2, device=self.dev, generator=gen) * torch.tensor([self.do_max, 15.0], device=self.dev)
             self.pool_rows = [pool[k] for k in range(64)]      # the [N, 2] views, made once: indexing a tensor costs the host ~2 us per call
         self.n_rows = len(self.pool_rows)
-        self.state = {"episode": 0, "in_episode": 0, "returns": None}
+        self.state = {"episode": 0, "in_episode": 0, "returns": None, "seed_base": 0}
+        self.last_rollout = None
         self.seg_events, self.graphs = [], {}
         self.gbufs = self.sh.gather_buffers(torch.float32)       # float64 row, float32 send, float32 [n_global] recv: allocated once
         self.status_snap = torch.empty(n_local, dtype=torch.float64, device=self.dev)
@@ -446,7 +481,7 @@ class StepLeg:
 
     # ---- the workload
     def reset(self):
-        self.env.reset(seed=1000 + self.state["episode"], scenario=self.scenario, rnd=self.rnd0)
+        self.env.reset(seed=1000 + self.state["episode"] - self.state["seed_base"], scenario=self.scenario, rnd=self.rnd0)
         self.state["episode"] += 1
         self.state["in_episode"] = 0
 
@@ -507,7 +542,7 @@ class StepLeg:
                 e0, e1 = self.event_pool.pop(), self.event_pool.pop()      # created before the timed region: no harness work in it
                 e0.record()
             if self.fused:
-                self.env.rollout(m, policy_seed=77)
+                self.last_rollout = self.env.rollout(m, policy_seed=77)
             else:
                 self.issue_steps(st["in_episode"], m)
             if record:
@@ -580,6 +615,7 @@ class StepLeg:
             if n_more is not None:
                 n_more -= 1
         t_primed = time.perf_counter()
+        self.state["seed_base"] = self.state["episode"]          # the next reset seed no longer depends on how long priming took
         if self.state["in_episode"] == CALLS_PER_EPISODE:         # the advance, warm-up and timing start at the first call of an episode
             self.end_of_episode()
             self.reset()
@@ -609,6 +645,13 @@ class StepLeg:
         return {"elapsed": elapsed, "dev_ms": dev_ms, "launches": launches, "segments": len(self.seg_events),
                 "host_issue_ms": (t_issued - t0) * 1e3, "gap_ms": gap_ms, "resets_timed": self.state["episode"] - episodes_before,
                 "timed_calls": [c for lo, hi in self.acct["call_ranges"] for c in range(lo, hi)]}
+
+    def outputs(self):
+        """What the last step() (fused: the last rollout()) returned to its caller."""
+        if self.fused:
+            return {"rollout_reward_sum": self.last_rollout}
+        e = self.env
+        return {"obs": e.obs, "state": e.state, "reward": e.reward, "done": e.done}
 
     def device_plan_counts(self, calls, actions=None):
         """What cfg.scheme = 1 did on THIS leg's envs, counted on the device (round 6): one more episode of the same envs (the next
@@ -688,21 +731,32 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1852)       # four episodes
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 1852 = four episodes; 64 cycles for --workload cycle)")
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="config2", choices=["config1", "config2", "config5", "cycle"])
     ap.add_argument("--envs-per-gpu", type=int, default=None)
     ap.add_argument("--policy", default="physical", choices=["physical", "uniform", "walk"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-large-leg", action="store_true", help="skip the in-run 262144-env leg (roofline.larger_batches['262144'])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the in-run 262144-env leg, the device-counted step statistics and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-large-leg", action="store_true", help="with --full: skip the in-run 262144-env leg (roofline.larger_batches['262144'])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32/float64, at most 64 MB)")
     ap.add_argument("--no-graphs", action="store_true", help="issue every step launch eagerly (one ctypes call per step)")
     ap.add_argument("--scheme", type=int, default=None, choices=[0, 1],
                     help="cfg.scheme: 1 (library default) adaptive Butcher-5 per interval, 0 ten RK4 substeps (rounds 1-4)")
     args = ap.parse_args(argv)
+    if args.steps is None:
+        args.steps = 64 if args.workload == "cycle" else 1852
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.policy == "walk" and args.workload in ("config5", "cycle"):
         raise SystemExit("--policy walk is a per-step policy: the fused rollout draws its actions on the device, the per-cycle env takes three set-points per cycle")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(self_launch(args, argv))
+        # the ranks run from the repository root: hand them the dump directory as an absolute path
+        raise SystemExit(self_launch(args, argv + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])))
 
     # Native libraries print to fd 1 (RCCL writes a five-line version banner when a communicator is created); the contract is
     # ONE JSON line on stdout, so fd 1 points at stderr until the result is printed.
@@ -771,6 +825,8 @@ def main(argv=None):
     env = leg.env
     m = leg.measure(args.steps, args.warmup, start_call)
     elapsed = m["elapsed"]
+    if args.dump_outputs and rank == 0:                  # before anything else runs on this handle
+        dump_outputs(args.dump_outputs, leg.outputs())
     rank_elapsed, rank_devices = [elapsed], ["cuda:%d %s" % (dev_index, torch.cuda.get_device_name(dev))]
     if dist_up:
         # one small all-gather AFTER the timed region: every rank's own time and device, so that the line says whether RCCL saw
@@ -798,7 +854,7 @@ def main(argv=None):
 
     # ---- the in-run large-batch leg: 262 144 envs on this one GPU, the same workload, bracket and K
     large = None
-    if (world == 1 and not dist_up and args.workload == "config2" and args.envs_per_gpu is None and not args.no_large_leg
+    if (args.full and world == 1 and not dist_up and args.workload == "config2" and args.envs_per_gpu is None and not args.no_large_leg
             and rank == 0):
         lleg = StepLeg(torch, dist, args, cfg, LARGE_LEG_ENVS, 0, 1, dev_index, False)
         lm = lleg.measure(args.steps, args.warmup, start_call)
@@ -858,9 +914,9 @@ def main(argv=None):
     # What cfg.scheme = 1 did on the timed envs, counted ON THE DEVICE (round 6; until then: the CPU oracle's sample): a replay of
     # the timed calls of one episode with the plan row read after every call.  After the timed region, untimed.
     counts = None
-    if scheme == 1 and not fused and rank == 0:
+    if args.full and scheme == 1 and not fused and rank == 0:
         counts = leg.device_plan_counts(sorted(set(timed_calls))[:CALLS_PER_EPISODE])
-    elif scheme == 1 and fused and rank == 0:
+    elif args.full and scheme == 1 and fused and rank == 0:
         # the fused kernel reports no plan (its state never leaves the registers): take the actions its policy draws for one more
         # episode and step through sbr_step with them - the same states to rounding, and the plan row says what each interval took
         leg.reset()
@@ -869,7 +925,7 @@ def main(argv=None):
         del racts
     # The CPU baseline (rank 0 of a 1-GPU run), after the timed region.  Its first pass also counts what the integrator did on
     # ITS sample of the workload (other random draws): kept as a cross-check of the device's count.
-    cpu = cpu_baseline(policy=args.policy, scheme=scheme) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    cpu = cpu_baseline(policy=args.policy, scheme=scheme) if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
 
     def over_timed_calls(key):
         v = cpu["per_call"].get(key) if cpu else None

@@ -50,7 +50,7 @@ def table(tag):
         ("**262 144 envs on the one GPU, timed INSIDE the same command** (`roofline.larger_batches[\"262144\"]`, a second handle, the same bracket, "
          "window and K; `%s`)" % bigd["kernel"],
          "the driver's command: %.1f µs per step = **%.3f of the prescribed roofline by the wall clock** (%.3f by events), %.3ge9 env-steps/s; "
-         "`python bench.py` (four whole episodes, resets and terminal calls inside): %.1f µs = %.3f (%.3f by events), %.3ge9"
+         "`python bench.py --full` (four whole episodes, resets and terminal calls inside): %.1f µs = %.3f (%.3f by events), %.3ge9"
          % (bigd["ms_per_step"] * 1e3, bigd["frac_wall"], bigd["frac_timed_launches"], bigd["env_steps_per_s"] / 1e9,
             big["ms_per_step"] * 1e3, big["frac_wall"], big["frac_timed_launches"], big["env_steps_per_s"] / 1e9),
          "`%s_bench_config2_driver_style.json`, `%s_bench_config2.json`" % (tag, tag)),
@@ -131,8 +131,8 @@ def headline(tag):
         ref = json.load(f)
     kt, cpu = pmc["kernel_trace"], c2["cpu_baseline"]
     return ("* `SBROS-v1` — the step-level env (`SbrOS`): `sbr_reset` / `sbr_step` / fused `sbr_rollout`; **%.3ge9 env-steps/s** per step call at\n"
-            "  65 536 envs on one MI355X (`python bench.py`, `profiles/%s_bench_config2.json`; with round 4's integrator, `--scheme 0`, on the same\n"
-            "  box: %.3ge9), `k_step` %.2f µs per launch by the rocprof average of whole episodes = %.3f of the prescribed HBM roofline (round 4:\n"
+            "  65 536 envs on one MI355X (`python bench.py --full`, `profiles/%s_bench_config2.json`; with round 4's integrator, `--scheme 0`, on the\n"
+            "  same box: %.3ge9), `k_step` %.2f µs per launch by the rocprof average of whole episodes = %.3f of the prescribed HBM roofline (round 4:\n"
             "  13.32 µs, 0.315); **262 144 envs on the same GPU, timed inside the same command: %.3f by the wall clock** (%.3ge9 env-steps/s); %.3ge10 in the\n"
             "  fused rollout (the Python reference: %.0f env-steps/s per core, `oracle/time_reference.py`; its C port %.2ge6 on one core of the GPU\n"
             "  box, %.2ge7 on %d)."

@@ -236,3 +236,35 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did(monkeypatch, capsys):
     with pytest.raises(SystemExit) as ex:
         bench.main(["--gpus", "2"])
     assert "cmd" not in calls and "WORLD_SIZE=3" in str(ex.value.code)
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_above_the_limit(tmp_path):
+    """--dump-outputs: one <name>.npy per array in float32 / float64 (flags become float32); above the size limit the same seeded
+    sample of env rows from every array, its indices beside them, and the same sample every time."""
+    import numpy as np
+    rs = np.random.RandomState(3)
+    arrays = {"obs": rs.rand(1000, 18).astype(np.float32), "x": rs.rand(1000), "done": (rs.rand(1000) < 0.5).astype(np.uint8)}
+    d = str(tmp_path / "all")
+    assert bench.dump_outputs(d, arrays) == ["done", "obs", "x"]
+    back = {n: np.load(os.path.join(d, n + ".npy")) for n in ("obs", "x", "done")}
+    assert back["obs"].dtype == np.float32 and back["x"].dtype == np.float64 and back["done"].dtype == np.float32
+    assert np.array_equal(back["obs"], arrays["obs"]) and np.array_equal(back["x"], arrays["x"]) and np.array_equal(back["done"], arrays["done"])
+    limit = 20000
+    for k in range(2):
+        d = str(tmp_path / ("sampled%d" % k))
+        assert bench.dump_outputs(d, arrays, max_bytes=limit) == ["done", "obs", "sample_env_index", "x"]
+        got = {n: np.load(os.path.join(d, n + ".npy")) for n in ("obs", "x", "done", "sample_env_index")}
+        assert sum(os.path.getsize(os.path.join(d, f)) - 128 for f in os.listdir(d)) <= limit      # minus the .npy headers
+        idx = got["sample_env_index"].astype(np.int64)
+        assert len(idx) > 100 and np.all(np.diff(idx) > 0)
+        assert np.array_equal(got["obs"], arrays["obs"][idx]) and np.array_equal(got["x"], arrays["x"][idx])
+        if k:
+            assert np.array_equal(idx, first)
+        first = idx
+
+
+def test_bench_rejects_a_step_count_below_one():
+    import pytest
+    with pytest.raises(SystemExit) as ex:
+        bench.main(["--steps", "0"])
+    assert ex.value.code == 2

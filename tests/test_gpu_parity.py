@@ -1772,7 +1772,8 @@ def test_output_rows_to_misaligned_destinations(G):
 @pytest.mark.gpu
 @pytest.mark.parametrize("force_dist", [False, True, "launcher"])
 def test_bench_line_contract(force_dist):
-    """bench.py as the driver runs it (`--gpus 1 --steps 20 --warmup 5`), in its own process; with force_dist the process group,
+    """bench.py with the driver's arguments and `--full` (`--gpus 1 --steps 20 --warmup 5 --full`: the large-batch leg and the
+    device-counted step statistics run too), in its own process; with force_dist the process group,
     the barrier of the bracket and the all-gather run over RCCL with one rank (what every rank of an N > 1 run executes);
     "launcher": the same under `python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1`, the
     driver's command line for N > 1 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the launcher's environment).
@@ -1780,7 +1781,7 @@ def test_bench_line_contract(force_dist):
     import json, os, subprocess, sys
     from conftest import ROOT
     env = dict(os.environ, SBR_BENCH_FORCE_DIST="1" if force_dist else "0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"]
     if force_dist == "launcher":
         args = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                 "--master-port", "29541"] + args
@@ -1854,14 +1855,45 @@ def test_bench_line_contract(force_dist):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full times the K steps and nothing else (no large-batch leg, no device
+    step count, no CPU baseline); --dump-outputs writes what the last timed sbr_step returned, and two runs with the same
+    arguments write the same arrays, bit for bit."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    outs = []
+    for k in range(2):
+        d_ = str(tmp_path / ("run%d" % k))
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                            "--dump-outputs", d_], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 20 and d["warmup"] == 5 and d["roofline"]["launches_timed"] == 20 and d["config"]["timed_calls"] == [41, 61]
+        assert abs(d["value"] - 65536 * 20 / (d["ms_per_step"] * 20e-3)) < 1e-6 * d["value"] and d["value"] > 1e9
+        assert "cpu_baseline" not in d and d["roofline"]["fp64_valu"]["b5_steps_per_interval"]["source"] is None
+        lb = d["roofline"]["larger_batches"]
+        assert lb is None or not any(v.get("measured_in_this_run") for v in lb.values())
+        arrs = {n: np.load(os.path.join(d_, n + ".npy")) for n in ("obs", "state", "reward", "done")}
+        assert sorted(os.listdir(d_)) == ["done.npy", "obs.npy", "reward.npy", "state.npy"]
+        assert arrs["obs"].shape == (65536, 18) and arrs["state"].shape == (65536, 15) and arrs["reward"].shape == arrs["done"].shape == (65536,)
+        assert all(a.dtype == np.float32 for a in arrs.values()) and all(np.isfinite(a).all() for a in arrs.values())
+        assert not arrs["done"].any()                                  # call 60 of an episode is not its last
+        outs.append(arrs)
+    for n in outs[0]:
+        assert np.array_equal(outs[0][n], outs[1][n]), n
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("policy", ["walk", "uniform"])
 def test_bench_secondary_policy_lines(policy):
     """`--policy walk` (the reference's own action model, get_available_actions :440-459) and `--policy uniform`
     (SURVEY.md 8d's synthetic inputs) are SECONDARY bench lines: same contract, labelled, never the headline."""
     import json, os, subprocess, sys
     from conftest import ROOT
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--policy", policy, "--steps", "30", "--warmup", "5", "--no-cpu-baseline",
-                        "--no-large-leg"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--policy", policy, "--steps", "30", "--warmup", "5", "--full",
+                        "--no-cpu-baseline", "--no-large-leg"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     c, r = d["config"], d["roofline"]
