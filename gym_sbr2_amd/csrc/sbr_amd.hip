@@ -21,10 +21,8 @@
 #include <new>
 #include <string>
 
-#ifndef SBR_BLOCK
 #define SBR_BLOCK 256     // threads per workgroup of the stepping kernels: four waves, one per SIMD.  Measured at N = 65536
                           // (round 1): 64 -> 23.0 us, 128 -> 22.8, 256 -> 22.65 per k_step launch (fewer workgroups to dispatch)
-#endif
 #include "sbr_device.h"
 
 #define SBR_RESET_BLOCK 256     // k_reset stages 84 KiB of tables in LDS: one block per CU, so make it four waves
@@ -61,25 +59,13 @@ struct SbrBuf {
 #define SBR_STAMP(k, drain) do { } while (0)
 #endif
 
-// How the stepping kernels' stores leave the CU: 0 plain, 1 agent-scope write-through (sc1), 2 non-temporal (nt), 3 system-scope
-// write-through (sc0 sc1).  Plain stores leave ~21 MB dirty in the L2s for the end-of-kernel write-back, which then sits
-// between two dependent launches; written through, the bytes drain while other waves still compute.  Measured per k_step
-// launch (profiles/r02_notes.md): 65536 envs 16.06 -> 15.5 us, 131072 envs 28.6 -> 23.1 us; nt gains half of that at 65536 and
-// nothing at 131072; sc0 sc1 equals sc1.
-#ifndef SBR_ST_MODE
-#define SBR_ST_MODE 1
-#endif
+// The stepping kernels' stores leave the CU as agent-scope write-through (sc1).  Plain stores leave ~21 MB dirty in the L2s
+// for the end-of-kernel write-back, which then sits between two dependent launches; written through, the bytes drain while
+// other waves still compute.  Measured per k_step launch (profiles/r02_notes.md): 65536 envs 16.06 -> 15.5 us, 131072 envs
+// 28.6 -> 23.1 us; non-temporal (nt) stores gain half of that at 65536 and nothing at 131072; sc0 sc1 equals sc1.
 template <typename T>
 SBR_DEV void st_out(T* p, T v) {
-#if SBR_ST_MODE == 1
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#elif SBR_ST_MODE == 2
-    __builtin_nontemporal_store(v, p);
-#elif SBR_ST_MODE == 3
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
-    *p = v;
-#endif
 }
 typedef unsigned int sbr_u32x4 __attribute__((ext_vector_type(4)));
 // The output staging of k_step reuses the wave's LDS parking region (declared double[]) for rows of OutT and reads it back as
@@ -97,15 +83,7 @@ template <> struct SbrAliasOf<double> { using type = sbr_f64_alias; };
 // issued back to back: the 64-bit address of the NEXT store was formed in the low half of the data registers of the previous
 // one).  The s_nop supplies the two wait states the compiler would have inserted for a store it knows.
 SBR_DEV void st_out16(sbr_u32x4* p, sbr_u32x4 v) {
-#if SBR_ST_MODE == 1
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-#elif SBR_ST_MODE == 2
-    __builtin_nontemporal_store(v, p);
-#elif SBR_ST_MODE == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-#else
-    *p = v;
-#endif
 }
 
 // Addressing.  An env is (i0, l): i0 = first env of the workgroup (wave-uniform, lives in SGPRs), l = threadIdx.x.  Every
@@ -542,10 +520,7 @@ SBR_DEV void store_rows2(OutT* __restrict__ rows_a, OutT* __restrict__ rows_b, u
 // wave's critical path (PMC, round 4: SQ_WAIT_ANY is what grew when an unrelated code change added two late scalar loads,
 // +0.3 us per launch).  So every line of the segment is touched ONCE, all at the same time, at wave start: the misses
 // overlap each other and the ~2 us of global-load latency, and every later scalar load of a constant hits the scalar cache.
-// The loads target one scratch SGPR whose value is never used.
-#ifndef SBR_KERNARG_WARM
-#define SBR_KERNARG_WARM 1     // 0 switches the warm-up off (A/B builds only; measured: profiles/r04_ab_kernarg_warm_modes.log)
-#endif
+// The loads target one scratch SGPR whose value is never used (measured: profiles/r04_ab_kernarg_warm_modes.log).
 #define SBR_WARM_LINES                                                                                                            \
         "s_load_dword %0, %1, 0x40\n s_load_dword %0, %1, 0x80\n s_load_dword %0, %1, 0xc0\n s_load_dword %0, %1, 0x100\n"        \
         "s_load_dword %0, %1, 0x140\n s_load_dword %0, %1, 0x180\n s_load_dword %0, %1, 0x1c0\n s_load_dword %0, %1, 0x200\n"     \
@@ -576,16 +551,7 @@ SBR_DEV void sbr_warm_kernarg_wait(uint32_t t) { asm volatile("s_waitcnt lgkmcnt
 // or a trace buffer), taken on the host: until round 4 that test read two fields of `p` and one of `b0`, and the s_waitcnt
 // in front of it held back EVERY global load of the wave for a scalar round trip to the argument segment.
 #define SBR_KF_NEED_M2 1u
-#define SBR_KF_STAGGER 2u
-#ifndef SBR_STAGGER_SLEEP
-#define SBR_STAGGER_SLEEP 25        // x 64 cycles
-#endif
-#ifndef SBR_STAGGER_MIN_ENVS
-#define SBR_STAGGER_MIN_ENVS 0      // every launch in 256-thread workgroups (> SBR_SMALL_BATCH envs); A/B builds move the window
-#endif
-#ifndef SBR_STAGGER_MAX_ENVS
-#define SBR_STAGGER_MAX_ENVS (1ll << 62)
-#endif
+#define SBR_KF_STAGGER 2u           // set by the host on every launch in 256-thread workgroups
 // trajectory export: the NO3-PID's e / ie / dcv of every interval go straight to the call's trace record while the PID runs
 // (slot _FIRST for the first interval of the call, the plain slots for the last one run), so that nothing has to be carried
 // across the integration for it.  Off (b.trace == NULL, the default) this is one untaken scalar branch per interval.
@@ -595,7 +561,8 @@ struct SbrTraceRec {
     int64_t env;                  // index of the lane's env in the handle
     SBR_DEV void pid(int iv, double e, double ie, double dcv) const {
         if (__builtin_expect(b.trace != nullptr, 0)) {
-            const int64_t steps = (int64_t)((int)(*meta_lds) >> SBR_META_STEPS_SHIFT);      // meta = steps*64 + flags
+            // meta = steps*16384 + plan*64 + m1i*32 + idle*16 + status*2 + done
+            const int64_t steps = (int64_t)((int)(*meta_lds) >> SBR_META_STEPS_SHIFT);
             if (env < b.n_trace && steps < b.trace_cap) {
                 double* rec = b.trace + (steps * SBR_NTRACE) * b.n_trace + env;
                 if (iv == 0) {
@@ -607,9 +574,6 @@ struct SbrTraceRec {
     }
 };
 
-#ifndef SBR_STEP_MIN_BLOCKS
-#define SBR_STEP_MIN_BLOCKS 1      // A/B builds: 2 caps k_step<.., 256, ..> at 256 registers (two waves per SIMD)
-#endif
 // WAVES = 2 (scheme 1, launches with more wavefronts than the chip has SIMDs): the register budget of two resident waves per SIMD
 // (256).  The scheme-1 step loops need 320 registers with everything the call carries across them; this build parks that - 13
 // controller values per interval, 7 of the call, 19 around the idle phase of the done call - in the lane's LDS slots (64 KiB per
@@ -617,7 +581,7 @@ struct SbrTraceRec {
 // Same arithmetic, same bits.  Measured (profiles/r05_ab_two_waves.log): 65 536 envs 12.8 against 12.2 us per call (one wave per
 // SIMD either way: the host keeps WAVES = 1 there), 131 072 envs 20.1 against 23.3, 262 144 envs 36.1 against 44.5.
 template <typename OutT, typename ActT, int BLK, bool OCI, int SCH, int WAVES = 1>
-__global__ __launch_bounds__(BLK, BLK == 256 ? (WAVES == 2 ? 2 : SBR_STEP_MIN_BLOCKS) : 1) void k_step(double* __restrict__ bx, double* __restrict__ bctrl, int64_t bn,
+__global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(double* __restrict__ bx, double* __restrict__ bctrl, int64_t bn,
                                                       const ActT* __restrict__ action, uint32_t flags, OutT* __restrict__ obs,
                                                       OutT* __restrict__ state, OutT* __restrict__ reward,
                                                       uint8_t* __restrict__ done, SbrPar p, SbrBuf b0) {
@@ -645,14 +609,12 @@ __global__ __launch_bounds__(BLK, BLK == 256 ? (WAVES == 2 ? 2 : SBR_STEP_MIN_BL
     double x[SBR_NX];
     SbrCtl c;
     SBR_STAMP(0, false);
-#if SBR_KERNARG_WARM
     const uint32_t warm_token = sbr_warm_kernarg_issue();
-#endif
     // Staggered entry (SBR_KF_STAGGER, large batches): every other workgroup of an XCD (workgroup g runs on XCD g % 8, so bit 3
     // of the index alternates inside one) waits ~0.65 us before its loads.  With one wave per SIMD every wave of the chip
     // otherwise loads at the same moment and stores at the same moment; half a microsecond of skew inside each XCD takes the
     // two bursts apart (measured: profiles/r04_notes.md, "staggered entry").
-    if ((flags & SBR_KF_STAGGER) != 0u && ((blockIdx.x >> 3) & 1u) != 0u) __builtin_amdgcn_s_sleep(SBR_STAGGER_SLEEP);
+    if ((flags & SBR_KF_STAGGER) != 0u && ((blockIdx.x >> 3) & 1u) != 0u) __builtin_amdgcn_s_sleep(25);   // x 64 cycles
     // every load below has an address that depends on nothing loaded: ONE memory round trip (the ring used to be read
     // in logical order, whose rows depend on t: a second, dependent round trip)
     load_x(b, i0, l, x);
@@ -665,9 +627,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 ? (WAVES == 2 ? 2 : SBR_STEP_MIN_BL
     const double a0 = (double)act[2 * l], a1 = (double)act[2 * l + 1];           // one 8- or 16-byte load per lane
     c.kla_last = CTRL(R_KLA_LAST);
     const double w8_0 = CTRL(R_W8), ret0 = CTRL(R_RET);
-#if SBR_KERNARG_WARM
     sbr_warm_kernarg_wait(warm_token);
-#endif
     my[SBR_PK_RET * 64] = ret0; my[SBR_PK_META * 64] = meta0; my[SBR_PK_W8 * 64] = w8_0;
     // (The compiler sinks the action load into the `not done` branch below - one global_load behind the branch in the ISA.
     // Pinning it into the batch above was measured SLOWER, profiles/r04_ab_kernarg_warm_and_pinned_loads.log: left alone.)
@@ -701,14 +661,11 @@ __global__ __launch_bounds__(BLK, BLK == 256 ? (WAVES == 2 ? 2 : SBR_STEP_MIN_BL
         if ((flags & SBR_KF_NEED_M2) == 0u) { c.so_m2 = c.so_m1; c.sno_m2 = c.sno_m1; }
         SBR_STAMP(2, false);
         const SbrTraceRec tr{b, my + SBR_PK_META * 64, i0 + l};
-#ifndef SBR_STEP_LOOP
-#define SBR_STEP_LOOP false     // straight-line: the second interval of a phase-boundary call out of line (247 VGPRs; the loop form needs 278 with the dependent ring loads live across the integration)
-#endif
         if constexpr (PARK) {
             x6.park(13, lv[0]); x6.park(14, lv[1]); x6.park(15, lv[2]); x6.park(16, kla_before); x6.park(17, v0); x6.park(18, si0);
             x6.park(19, xi0);
         }
-        sbr_run_intervals<SBR_STEP_LOOP, SCH>(p, c, x, a0, a1, x6, tr);
+        sbr_run_intervals<SCH>(p, c, x, a0, a1, x6, tr);
         double kla_before_r = kla_before, v0_r = v0, si0_r = si0, xi0_r = xi0;
         if constexpr (PARK) {
             asm volatile("" : "+v"(l) : : "memory");  // the row addresses of the stores are formed again from here (not kept across the integration)
@@ -864,7 +821,7 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout(SbrPar p, SbrBuf b
         if (finished) continue;
         double t_obs;
         bool dn;
-        sbr_run_intervals<false, SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
+        sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
         x6.get(xa6);
         SbrHistReg hs{hist};
         const double r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, qw, ksum, rp);
@@ -1201,39 +1158,34 @@ static void derive_params(const sbr_config& c, SbrPar& p) {
     }
 }
 
-// up to 1.5 waves per SIMD (MI355X: 98304 envs) the fused scheme-1 kernels run their uncapped-register build
-#ifdef SBR_ONE_WAVE_MAX_ENVS
-#define SBR_FUSED_ONE_WAVE_ENVS(e) ((int64_t)(SBR_ONE_WAVE_MAX_ENVS))
-#else
-#define SBR_FUSED_ONE_WAVE_ENVS(e) ((e)->one_wave_envs + (e)->one_wave_envs / 2)
-#endif
-// A launch with more wavefronts than the device has SIMDs (MI355X: 1024 SIMDs x 64 lanes = 65536 envs; a partitioned device has
-// fewer) runs the two-waves-per-SIMD build of the scheme-1 k_step.  A/B builds fix the threshold with -DSBR_STEP_ONE_WAVE_MAX_ENVS=n.
-#ifdef SBR_STEP_ONE_WAVE_MAX_ENVS
-#define SBR_STEP_ONE_WAVE_ENVS(e) ((int64_t)(SBR_STEP_ONE_WAVE_MAX_ENVS))
-#else
-#define SBR_STEP_ONE_WAVE_ENVS(e) ((e)->one_wave_envs)
-#endif
-#ifndef SBR_SMALL_BATCH
+// Launch shapes.  Each decision is taken once, here: the launch sites and sbr_query both read these functions.
 #define SBR_SMALL_BATCH 49152       // up to this many envs k_step runs in 64-thread workgroups (measured: profiles/r02_ab_block.log)
-#endif
+static int step_block(const sbr_env* e) { return e->n <= SBR_SMALL_BATCH ? 64 : 256; }
+// A launch with more wavefronts than the device has SIMDs (MI355X: 1024 SIMDs x 64 lanes = 65536 envs; a partitioned device has
+// fewer) runs the two-waves-per-SIMD build of the scheme-1 k_step.
+static int64_t step_two_waves_above(const sbr_env* e) { return e->one_wave_envs > SBR_SMALL_BATCH ? e->one_wave_envs : SBR_SMALL_BATCH; }
+static int step_waves(const sbr_env* e) { return e->cfg.scheme == 1 && e->n > step_two_waves_above(e) ? 2 : 1; }
+// up to 1.5 waves per SIMD (MI355X: 98304 envs) the fused scheme-1 kernels (k_rollout, k_cycle) run their uncapped-register build
+static int64_t fused_one_wave_max(const sbr_env* e) { return e->one_wave_envs + e->one_wave_envs / 2; }
+static int fused_waves(const sbr_env* e) { return e->cfg.scheme == 1 && e->n <= fused_one_wave_max(e) ? 1 : 2; }
+// more waves than SIMDs: k_reset in 512-thread workgroups, two waves per SIMD
+static int reset_block(const sbr_env* e) { return e->n > e->one_wave_envs ? 512 : SBR_RESET_BLOCK; }
+// the reset kernels of output type T, indexed by CARRY: k_reset in workgroups of BLK threads, k_cycle_reset (same arguments)
+template <typename T> using ResetFn = decltype(&k_reset<T, false>);
+template <typename T, int BLK> constexpr ResetFn<T> kReset[2] = {k_reset<T, false, BLK>, k_reset<T, true, BLK>};
+template <typename T> constexpr ResetFn<T> kCycleReset[2] = {k_cycle_reset<T, false>, k_cycle_reset<T, true>};
+
 template <typename OutT, typename ActT, bool OCI, int SCH>
 static void launch_step_k(sbr_env* e, const void* action, void* obs, void* state, void* reward, uint8_t* done,
                           hipStream_t st) {
-    const uint32_t flags = (e->par.KcD_DO != 0.0 || e->par.KcD_EC != 0.0 || e->buf.trace != nullptr) ? SBR_KF_NEED_M2 : 0u;
-    if (e->n <= SBR_SMALL_BATCH)
-        hipLaunchKernelGGL((k_step<OutT, ActT, 64, OCI, SCH>), dim3((unsigned)((e->n + 63) / 64)), dim3(64), 0, st, e->buf.x, e->buf.ctrl,
-                           e->buf.n, (const ActT*)action, flags, (OutT*)obs, (OutT*)state, (OutT*)reward, done, e->par, e->buf);
-    else if (SCH == 1 && e->n > SBR_STEP_ONE_WAVE_ENVS(e))
-        hipLaunchKernelGGL((k_step<OutT, ActT, 256, OCI, SCH, SCH == 1 ? 2 : 1>), dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, st,
-                           e->buf.x, e->buf.ctrl, e->buf.n, (const ActT*)action,
-                           flags | ((e->n >= SBR_STAGGER_MIN_ENVS && e->n <= SBR_STAGGER_MAX_ENVS) ? SBR_KF_STAGGER : 0u), (OutT*)obs,
-                           (OutT*)state, (OutT*)reward, done, e->par, e->buf);
-    else
-        hipLaunchKernelGGL((k_step<OutT, ActT, 256, OCI, SCH>), dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, st, e->buf.x,
-                           e->buf.ctrl, e->buf.n, (const ActT*)action,
-                           flags | ((e->n >= SBR_STAGGER_MIN_ENVS && e->n <= SBR_STAGGER_MAX_ENVS) ? SBR_KF_STAGGER : 0u), (OutT*)obs,
-                           (OutT*)state, (OutT*)reward, done, e->par, e->buf);
+    const int blk = step_block(e);
+    const uint32_t flags = ((e->par.KcD_DO != 0.0 || e->par.KcD_EC != 0.0 || e->buf.trace != nullptr) ? SBR_KF_NEED_M2 : 0u) |
+                           (blk == 256 ? SBR_KF_STAGGER : 0u);
+    // scheme 0 has no two-waves build (step_waves is 1 for it)
+    auto fn = k_step<OutT, ActT, 64, OCI, SCH>;
+    if (blk == 256) fn = step_waves(e) == 2 ? k_step<OutT, ActT, 256, OCI, SCH, SCH == 1 ? 2 : 1> : k_step<OutT, ActT, 256, OCI, SCH>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)((e->n + blk - 1) / blk)), dim3(blk), 0, st, e->buf.x, e->buf.ctrl, e->buf.n,
+                       (const ActT*)action, flags, (OutT*)obs, (OutT*)state, (OutT*)reward, done, e->par, e->buf);
 }
 template <typename OutT, typename ActT>
 static void launch_step(sbr_env* e, const void* action, void* obs, void* state, void* reward, uint8_t* done,
@@ -1241,6 +1193,17 @@ static void launch_step(sbr_env* e, const void* action, void* obs, void* state, 
     const bool oci = e->cfg.reward_kind == 2, b5 = e->cfg.scheme == 1;      // one instantiation per reward family and scheme
     if (oci) { if (b5) launch_step_k<OutT, ActT, true, 1>(e, action, obs, state, reward, done, st); else launch_step_k<OutT, ActT, true, 0>(e, action, obs, state, reward, done, st); }
     else { if (b5) launch_step_k<OutT, ActT, false, 1>(e, action, obs, state, reward, done, st); else launch_step_k<OutT, ActT, false, 0>(e, action, obs, state, reward, done, st); }
+}
+
+template <typename T, typename A>
+static void launch_cycle(sbr_env* e, const void* action, void* obs, void* reward, double* diag, hipStream_t st) {
+    const auto fn = e->cfg.scheme == 1 ? (fused_waves(e) == 1 ? k_cycle<T, A, 1, 1> : k_cycle<T, A, 1, 2>) : k_cycle<T, A, 0, 2>;
+    hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, st, e->par, e->buf, (const A*)action, (T*)obs, (T*)reward, diag);
+}
+template <bool OCI>
+static void launch_rollout(sbr_env* e, int32_t n_steps, uint64_t policy_seed, double* returns, float* actions_out, hipStream_t st) {
+    const auto fn = e->cfg.scheme == 1 ? (fused_waves(e) == 1 ? k_rollout<OCI, 1, 1> : k_rollout<OCI, 1, 2>) : k_rollout<OCI, 0, 2>;
+    hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, st, e->par, e->buf, n_steps, policy_seed, returns, actions_out);
 }
 
 extern "C" {
@@ -1362,7 +1325,8 @@ int sbr_create(int64_t n_envs, int device_id, int64_t first_env_id, const sbr_co
     CREATE_TRY(hipMemset(e->buf.ctrl, 0, R_NROWS * nb));
     CREATE_TRY(hipMemset(e->buf.infl, 0, SBR_NX * nb));
     // an env is unusable until its first reset: mark everything done so that step() is a no-op until then
-    // (meta = steps*64 + m1i*32 + idle*16 + status*2 + done  =>  1.0 = "done"); filled on the device, no host staging buffer
+    // (meta = steps*16384 + plan*64 + m1i*32 + idle*16 + status*2 + done  =>  1.0 = "done"); filled on the device, no host
+    // staging buffer
     hipLaunchKernelGGL(k_fill, grid_for(n_envs), dim3(SBR_BLOCK), 0, nullptr, e->buf.ctrl + (size_t)R_META * n_envs, n_envs, 1.0);
     CREATE_TRY(hipGetLastError());
     CREATE_TRY(hipDeviceSynchronize());
@@ -1370,14 +1334,12 @@ int sbr_create(int64_t n_envs, int device_id, int64_t first_env_id, const sbr_co
     CREATE_TRY(hipEventCreate(&e->ev1));
     {
         const int lds_bytes = kLdsTableDoubles * (int)sizeof(double);      // 84 KiB of dynamic LDS: above the 64 KiB default
-        const void* fns[8] = {reinterpret_cast<const void*>(&k_reset<float, false>), reinterpret_cast<const void*>(&k_reset<float, true>),
-                              reinterpret_cast<const void*>(&k_reset<double, false>), reinterpret_cast<const void*>(&k_reset<double, true>),
-                              reinterpret_cast<const void*>(&k_reset<float, false, 512>), reinterpret_cast<const void*>(&k_reset<float, true, 512>),
-                              reinterpret_cast<const void*>(&k_reset<double, false, 512>), reinterpret_cast<const void*>(&k_reset<double, true, 512>)};
-        for (const void* fn : fns) CREATE_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        const void* cfns[4] = {reinterpret_cast<const void*>(&k_cycle_reset<float, false>), reinterpret_cast<const void*>(&k_cycle_reset<float, true>),
-                               reinterpret_cast<const void*>(&k_cycle_reset<double, false>), reinterpret_cast<const void*>(&k_cycle_reset<double, true>)};
-        for (const void* fn : cfns) CREATE_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        for (const int c : {0, 1}) {
+            const void* fns[6] = {(const void*)kReset<float, SBR_RESET_BLOCK>[c], (const void*)kReset<double, SBR_RESET_BLOCK>[c],
+                                  (const void*)kReset<float, 512>[c], (const void*)kReset<double, 512>[c],
+                                  (const void*)kCycleReset<float>[c], (const void*)kCycleReset<double>[c]};
+            for (const void* fn : fns) CREATE_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        }
     }
 #undef CREATE_TRY
     e->buf.n = n_envs; e->buf.first_env_id = first_env_id;
@@ -1402,16 +1364,15 @@ const char* sbr_last_error(const sbr_env* e) { return e ? e->err.c_str() : g_cre
 
 int sbr_query(const sbr_env* e, int32_t what, int64_t* out) {
     if (!e || !out) return SBR_ERR_INVALID;
-    const bool b5 = e->cfg.scheme == 1;
     switch (what) {
         case SBR_Q_ONE_WAVE_ENVS: *out = e->one_wave_envs; break;
         case SBR_Q_STEP_SMALL_BATCH_ENVS: *out = SBR_SMALL_BATCH; break;
-        case SBR_Q_STEP_BLOCK: *out = e->n <= SBR_SMALL_BATCH ? 64 : 256; break;
-        case SBR_Q_STEP_WAVES: *out = (e->n > SBR_SMALL_BATCH && b5 && e->n > SBR_STEP_ONE_WAVE_ENVS(e)) ? 2 : 1; break;
-        case SBR_Q_STEP_TWO_WAVES_ABOVE_ENVS: *out = SBR_STEP_ONE_WAVE_ENVS(e) > SBR_SMALL_BATCH ? SBR_STEP_ONE_WAVE_ENVS(e) : SBR_SMALL_BATCH; break;
-        case SBR_Q_FUSED_ONE_WAVE_MAX_ENVS: *out = SBR_FUSED_ONE_WAVE_ENVS(e); break;
-        case SBR_Q_ROLLOUT_WAVES: *out = (b5 && e->n <= SBR_FUSED_ONE_WAVE_ENVS(e)) ? 1 : 2; break;
-        case SBR_Q_RESET_BLOCK: *out = e->n > e->one_wave_envs ? 512 : SBR_RESET_BLOCK; break;
+        case SBR_Q_STEP_BLOCK: *out = step_block(e); break;
+        case SBR_Q_STEP_WAVES: *out = step_waves(e); break;
+        case SBR_Q_STEP_TWO_WAVES_ABOVE_ENVS: *out = step_two_waves_above(e); break;
+        case SBR_Q_FUSED_ONE_WAVE_MAX_ENVS: *out = fused_one_wave_max(e); break;
+        case SBR_Q_ROLLOUT_WAVES: *out = fused_waves(e); break;
+        case SBR_Q_RESET_BLOCK: *out = reset_block(e); break;
         case SBR_Q_SCHEME: *out = e->cfg.scheme; break;
         default: return SBR_ERR_INVALID;
     }
@@ -1436,16 +1397,14 @@ static int reset_impl(sbr_env* e, bool carry, uint64_t seed, const int32_t* scen
     ON_DEVICE(e);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = influent ? 0 : kLdsTableDoubles * sizeof(double);
-    const bool wide = e->n > e->one_wave_envs;           // more waves than SIMDs: 512-thread workgroups, two waves per SIMD
-    const int bs = wide ? 512 : SBR_RESET_BLOCK;
-    const dim3 grid((unsigned)((e->n + bs - 1) / bs)), blk(bs);
-#define RESET_LAUNCH_B(T, C, B) hipLaunchKernelGGL((k_reset<T, C, B>), grid, blk, lds, st, e->par, e->buf, e->tables, seed, scenario, \
-                                                   rnd, influent, mask, (T*)obs)
-#define RESET_LAUNCH(T, C) do { if (wide) RESET_LAUNCH_B(T, C, 512); else RESET_LAUNCH_B(T, C, SBR_RESET_BLOCK); } while (0)
-    if (e->cfg.out_f64) { if (carry) RESET_LAUNCH(double, true); else RESET_LAUNCH(double, false); }
-    else { if (carry) RESET_LAUNCH(float, true); else RESET_LAUNCH(float, false); }
-#undef RESET_LAUNCH
-#undef RESET_LAUNCH_B
+    const int blk = reset_block(e);
+    const dim3 grid((unsigned)((e->n + blk - 1) / blk));
+    if (e->cfg.out_f64)
+        hipLaunchKernelGGL((blk == 512 ? kReset<double, 512> : kReset<double, SBR_RESET_BLOCK>)[carry], grid, dim3(blk), lds, st,
+                           e->par, e->buf, e->tables, seed, scenario, rnd, influent, mask, (double*)obs);
+    else
+        hipLaunchKernelGGL((blk == 512 ? kReset<float, 512> : kReset<float, SBR_RESET_BLOCK>)[carry], grid, dim3(blk), lds, st,
+                           e->par, e->buf, e->tables, seed, scenario, rnd, influent, mask, (float*)obs);
     HIP_TRY(e, hipGetLastError());
     return SBR_OK;
 }
@@ -1494,11 +1453,12 @@ int sbr_cycle_reset(sbr_env* e, uint64_t seed, const int32_t* scenario, const do
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = influent ? 0 : kLdsTableDoubles * sizeof(double);
     const dim3 grid((unsigned)((e->n + SBR_RESET_BLOCK - 1) / SBR_RESET_BLOCK)), blk(SBR_RESET_BLOCK);
-#define CRESET(T, C) hipLaunchKernelGGL((k_cycle_reset<T, C>), grid, blk, lds, st, e->par, e->buf, e->tables, seed, scenario, rnd, \
-                                        influent, mask, (T*)obs)
-    if (e->cfg.out_f64) { if (carry_over) CRESET(double, true); else CRESET(double, false); }
-    else { if (carry_over) CRESET(float, true); else CRESET(float, false); }
-#undef CRESET
+    if (e->cfg.out_f64)
+        hipLaunchKernelGGL(kCycleReset<double>[carry_over != 0], grid, blk, lds, st, e->par, e->buf, e->tables, seed, scenario, rnd,
+                           influent, mask, (double*)obs);
+    else
+        hipLaunchKernelGGL(kCycleReset<float>[carry_over != 0], grid, blk, lds, st, e->par, e->buf, e->tables, seed, scenario, rnd,
+                           influent, mask, (float*)obs);
     HIP_TRY(e, hipGetLastError());
     return SBR_OK;
 }
@@ -1507,14 +1467,13 @@ int sbr_cycle_step(sbr_env* e, const void* action, void* obs, void* reward, doub
     if (!e || !action) return fail(e, SBR_ERR_INVALID, "sbr_cycle_step: NULL env or action");
     ON_DEVICE(e);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid = grid_for(e->n), blk(SBR_BLOCK);
-#define CSTEP1(T, A, S, W) hipLaunchKernelGGL((k_cycle<T, A, S, W>), grid, blk, 0, st, e->par, e->buf, (const A*)action, (T*)obs, (T*)reward, diag)
-#define CSTEP(T, A) do { if (e->cfg.scheme == 1) { if (e->n <= SBR_FUSED_ONE_WAVE_ENVS(e)) CSTEP1(T, A, 1, 1); else CSTEP1(T, A, 1, 2); } \
-                         else CSTEP1(T, A, 0, 2); } while (0)
-    if (e->cfg.out_f64) { if (e->cfg.act_f64) CSTEP(double, double); else CSTEP(double, float); }
-    else { if (e->cfg.act_f64) CSTEP(float, double); else CSTEP(float, float); }
-#undef CSTEP
-#undef CSTEP1
+    if (e->cfg.out_f64) {
+        if (e->cfg.act_f64) launch_cycle<double, double>(e, action, obs, reward, diag, st);
+        else launch_cycle<double, float>(e, action, obs, reward, diag, st);
+    } else {
+        if (e->cfg.act_f64) launch_cycle<float, double>(e, action, obs, reward, diag, st);
+        else launch_cycle<float, float>(e, action, obs, reward, diag, st);
+    }
     HIP_TRY(e, hipGetLastError());
     return SBR_OK;
 }
@@ -1522,12 +1481,8 @@ int sbr_cycle_step(sbr_env* e, const void* action, void* obs, void* reward, doub
 int sbr_rollout(sbr_env* e, int32_t n_steps, uint64_t policy_seed, double* returns, float* actions_out, void* stream) {
     if (!e || n_steps < 0) return fail(e, SBR_ERR_INVALID, "sbr_rollout: bad argument");
     ON_DEVICE(e);
-#define ROLL(O, S, W) hipLaunchKernelGGL((k_rollout<O, S, W>), grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, \
-                                         n_steps, policy_seed, returns, actions_out)
-    const bool one_wave = e->cfg.scheme == 1 && e->n <= SBR_FUSED_ONE_WAVE_ENVS(e);
-    if (e->cfg.reward_kind == 2) { if (e->cfg.scheme == 1) { if (one_wave) ROLL(true, 1, 1); else ROLL(true, 1, 2); } else ROLL(true, 0, 2); }
-    else { if (e->cfg.scheme == 1) { if (one_wave) ROLL(false, 1, 1); else ROLL(false, 1, 2); } else ROLL(false, 0, 2); }
-#undef ROLL
+    if (e->cfg.reward_kind == 2) launch_rollout<true>(e, n_steps, policy_seed, returns, actions_out, (hipStream_t)stream);
+    else launch_rollout<false>(e, n_steps, policy_seed, returns, actions_out, (hipStream_t)stream);
     HIP_TRY(e, hipGetLastError());
     return SBR_OK;
 }

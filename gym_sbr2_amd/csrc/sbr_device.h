@@ -91,12 +91,6 @@ SBR_DEV double sbr_rcp(double d) {
     const double e = __builtin_fma(-d, r, 1.0);
     return __builtin_fma(r, __builtin_fma(e, e, e), r);
 }
-// the same Newton step from a reciprocal that is already within ~1e-7 of 1/d (1/V while carbon is dosed: V moves by
-// 3e-8 of itself per substep, so e^3 ~ 1e-23)
-SBR_DEV double sbr_rcp_refine(double d, double r) {
-    const double e = __builtin_fma(-d, r, 1.0);
-    return __builtin_fma(r, __builtin_fma(e, e, e), r);
-}
 
 // The components that feed back into the process rates, and therefore have to exist at every RK4 stage:
 // Ss Xs Xbh Xba So Sno Snh Snd Xnd.  V, Si, Xi and Salk never enter a rate; Xp does not either.
@@ -626,9 +620,6 @@ struct SbrX6Reg {
         for (int j = 0; j < SBR_NXD; ++j) o[j] = v[j];
     }
 };
-#ifndef SBR_BLOCK
-#define SBR_BLOCK 256
-#endif
 template <bool PARK>
 struct SbrX6LdsT {         // slot j of the lane lives at base[j * 64] inside its wave's region: conflict-free, 8-byte accesses
     // PARK (the two-waves-per-SIMD build of k_step): what the call keeps across the integration goes to the lane's slots behind
@@ -737,12 +728,8 @@ SBR_DEV void sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& x
     }
     int plan = 0;
     if constexpr (SCH == 1) {
-#ifdef SBR_B5_ONE_FORM
-        plan = sbr_b5a<true>(p, x, span, kla, ec);
-#else
         if (__builtin_amdgcn_ballot_w64(ec != 0.0) == 0ull) plan = sbr_b5a<false>(p, x, span, kla, 0.0);
         else plan = sbr_b5a<true>(p, x, span, kla, ec);
-#endif
     } else {
         const double h = span * p.inv_substeps;
         if (__builtin_amdgcn_ballot_w64(ec != 0.0) == 0ull) sbr_rk4<0>(p, x, h, p.substeps, kla, 0.0, nold);
@@ -772,48 +759,32 @@ SBR_DEV void sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& x
 // interval (3 times per episode).  A third cannot fire: sbr_create checks that every phase is longer than t_delta.
 // The four conditions are mutually exclusive for a given t, so the first one that fires is phase(t); after its interval t
 // has advanced, and a LATER test fires in the same call exactly when phase(t) has increased.
-// Two equivalent forms, chosen per kernel by measurement (profiles/r02_notes.md, r02_ab_phase_logic.log, r02_ab_loop2.log):
-//  LOOP = true   two passes of "run an interval if phase(t) is past the last one run", so that the interval code exists
-//                ONCE in the kernel (k_step is sensitive to code size: 14.33 us per launch; a loop over the reference's four
-//                tests 14.68; straight-line 14.9);
-//  LOOP = false  straight-line, the second interval behind an unlikely branch (k_rollout: 7.7 us per call against 8.0 - in a
-//                loop the plant is a loop-carried value, ~60 register copies per call).
+// Straight-line, the second interval behind an unlikely branch (the interval code exists twice), for register pressure.  A
+// two-pass loop ("run an interval if phase(t) is past the last one run") makes the plant a loop-carried value: ~60 register
+// copies per call in k_rollout (7.7 us per call against 8.0, profiles/r02_notes.md), and in k_step, whose dependent ring
+// loads are live across the integration, 278 VGPRs and AGPR spills against 247 (round 4, profiles/r04_notes.md).
 // Envs reset together are in lockstep, so the branches are wave-uniform in practice; divergent waves are still correct.
 SBR_DEV int sbr_phase(const SbrPar& p, double t) {
     // = t < T3_0 ? 0 : (t <= T3_end ? 1 : (t <= T4_end ? 2 : (t > T4_end ? 3 : -1))), as a sum of comparisons (no branches);
     // every comparison is false for a NaN: -1
     return (t >= p.T3_0 ? 1 : 0) + (t > p.T3_end ? 1 : 0) + (t > p.T4_end ? 1 : 0) - (t == t ? 0 : 1);
 }
-template <bool LOOP, int SCH, typename X6, typename TR>
+template <int SCH, typename X6, typename TR>
 SBR_DEV void sbr_run_intervals(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], double a0, double a1, X6& xs6, const TR& tr) {
     a0 = a0 < 0.0 ? 0.0 : (a0 > p.act_DO_max ? p.act_DO_max : a0);       // :901-906
     a1 = a1 < 0.0 ? 0.0 : (a1 > p.act_EC_max ? p.act_EC_max : a1);       // :865-870
     c.n_new = 0; c.st_new = 0; c.plans = 0;
     c.knew[0] = c.kla_last; c.knew[1] = c.kla_last;      // defined even if no interval runs (t injected as NaN: sbr_phase = -1)
-    if (LOOP) {
-        int last = -1;
-#pragma unroll 1
-        for (int it = 0; it < 2; ++it) {
-            const int ph = sbr_phase(p, c.t);
-            if (ph > last) {
-                const bool aerobic = (ph & 1) != 0;
-                c.u_do = aerobic ? a0 : 0.0; c.u_ec = aerobic ? 0.0 : a1;
-                sbr_interval<SCH>(p, c, x, xs6, aerobic, tr);
-                last = ph;
-            }
-        }
-    } else {
-        const int ph = sbr_phase(p, c.t);
-        if (ph >= 0) {
-            const bool aerobic = (ph & 1) != 0;
-            c.u_do = aerobic ? a0 : 0.0; c.u_ec = aerobic ? 0.0 : a1;
-            sbr_interval<SCH>(p, c, x, xs6, aerobic, tr);
-            const int ph2 = sbr_phase(p, c.t);
-            if (__builtin_expect(ph2 > ph, 0)) {
-                const bool aerobic2 = (ph2 & 1) != 0;
-                c.u_do = aerobic2 ? a0 : 0.0; c.u_ec = aerobic2 ? 0.0 : a1;
-                sbr_interval<SCH>(p, c, x, xs6, aerobic2, tr);
-            }
+    const int ph = sbr_phase(p, c.t);
+    if (ph >= 0) {
+        const bool aerobic = (ph & 1) != 0;
+        c.u_do = aerobic ? a0 : 0.0; c.u_ec = aerobic ? 0.0 : a1;
+        sbr_interval<SCH>(p, c, x, xs6, aerobic, tr);
+        const int ph2 = sbr_phase(p, c.t);
+        if (__builtin_expect(ph2 > ph, 0)) {
+            const bool aerobic2 = (ph2 & 1) != 0;
+            c.u_do = aerobic2 ? a0 : 0.0; c.u_ec = aerobic2 ? 0.0 : a1;
+            sbr_interval<SCH>(p, c, x, xs6, aerobic2, tr);
         }
     }
 }

@@ -1,5 +1,5 @@
 """Register / scratch footprint of the kernels for a set of -D flags (cross-compiled, no GPU):
-   python scripts/probes/regs.py "-DSBR_STEP_MIN_BLOCKS=2" [symbol-substring ...]"""
+   python scripts/probes/regs.py "-DSBR_STAMPS" [symbol-substring ...]"""
 import os
 import re
 import subprocess

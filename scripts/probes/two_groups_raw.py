@@ -6,7 +6,6 @@ no per-call Python objects): the host costs ~3.5 us per sbr_step call, so two ca
   two     2 handles x 32768 envs (first_env_id 0 / 32768), two streams, stepped alternately
   four    4 handles x 16384 envs, four streams
   graph2  the two chains captured fork/join into ONE HIP graph of 64 steps, replayed
-  two256  like `two`, for a library built with -DSBR_SMALL_BATCH=16384 (256-thread workgroups at 32768 envs)
 
 usage: python scripts/probes/two_groups_raw.py [modes ...] [--steps K] [--reps R] [--total N]
 Prints the period per step of ALL envs (wall clock between two device synchronisations, best and median of R repetitions,
@@ -137,7 +136,7 @@ def main():
     dev = torch.device("cuda", 0)
     print("library:", _capi.library_path(), "| steps", steps, "reps", reps, "total envs", total, flush=True)
     for m in modes:
-        ng = {"one": 1, "two": 2, "two256": 2, "four": 4, "graph2": 2, "eight": 8}[m]
+        ng = {"one": 1, "two": 2, "four": 4, "graph2": 2, "eight": 8}[m]
         gs = make_groups(ng, total, dev)
         if m == "graph2":
             run_graph2(gs, steps, reps, total)
