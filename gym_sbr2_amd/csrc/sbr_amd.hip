@@ -107,9 +107,7 @@ SBR_DEV void store_x(const SbrBuf& b, int64_t i0, uint32_t l, const double (&x)[
 //    count k is recovered from the running time, k = round((t - T_fill)/t_delta); a step writes ONE slot, not ten, and
 //    (round 4) READS three: next to the ring the handle keeps Kla[-1] and the sum of the eight entries before it, from which
 //    the reward's window follows incrementally (SbrHistInc in sbr_device.h);
-//  * steps, the plan of the last interval (round 6), two flags, status bits and the done flag share one row (meta = steps*16384 +
-//    plan*64 + m1i*32 + idle*16 + status*2 + done, an integer < 2^31 held in a double: steps saturate at 2^17 - 1 calls per
-//    episode; plan = SBR_C_PLAN's code, 8 bits);
+//  * steps, plan, two flags, status bits and the done flag share one row (SbrMeta);
 //  * So[-1] and Sno[-1] are IMPLICIT after an ordinary step (round 4): every interval ends with So.append(x_out[-1][8]),
 //    Sno.append(x_out[-1][9]) (:1955-1956, :2043-2044), so after a step the two values ARE x[8] and x[9] and k_step neither
 //    stores nor loads their rows (meta's m1i bit says so).  Whoever writes values that are NOT the plant's - the reset (Ss in
@@ -124,6 +122,33 @@ enum { R_T = 0, R_SO_M1, R_SNO_M1, R_IE_DO, R_IE_EC, R_EC_LAST, R_RET, R_META, R
        R_SO_M2 = R_RING0 + SBR_KLA_HIST, R_SNO_M2, R_QW, R_KSUM, R_NROWS };
 #define SBR_MAX_STEPS ((1 << 17) - 1)
 
+// The R_META row: an integer < 2^31 held in a double,
+//   meta = steps*16384 + plan*64 + m1i*32 + idle*16 + status*2 + done.
+// `steps`: calls of the episode, saturating at SBR_MAX_STEPS.  `plan`: what cfg.scheme = 1 did in the last control interval
+// k_step ran for this env (step count + 128 if dissolved oxygen was held; 0 = none reported: scheme 0, a reset, a rollout) -
+// SBR_C_PLAN of the public layout; it rides in this row so that reporting it moves no extra byte.  `idle`: the done call of
+// k_step appended one more Kla than t accounts for (Sim_idle's, :2578): the ring's oldest entry then sits one slot further than
+// ring_k(t) says.  `m1i`: So[-1], Sno[-1] are x[8], x[9] and their rows are stale (set by an ordinary k_step call only).
+// `status`: the sticky SBR_ST_* bits.  `done`: the episode has ended; step() leaves the env alone until a reset.
+struct SbrMeta {
+    int steps = 0, status = 0;
+    bool done = false, idle = false, m1i = false;
+    int plan = 0;
+    __host__ __device__ static constexpr double pack(SbrMeta m) {
+        return (double)((m.steps << kStepsShift) + ((m.plan & 0xff) << kPlanShift) + (m.m1i ? kM1i : 0) + (m.idle ? kIdle : 0) +
+                        m.status * 2 + (m.done ? kDone : 0));
+    }
+    static constexpr int kDone = 1, kIdle = 16, kM1i = 32, kPlanShift = 6, kStepsShift = 14;
+    SBR_DEV static SbrMeta unpack(double m) {
+        const int v = (int)m;
+        SbrMeta r;
+        r.done = (v & kDone) != 0; r.status = (v >> 1) & 7; r.idle = (v & kIdle) != 0; r.m1i = (v & kM1i) != 0;
+        r.plan = (v >> kPlanShift) & 0xff; r.steps = v >> kStepsShift;
+        return r;
+    }
+    SBR_DEV static int next_steps(int steps) { return steps < SBR_MAX_STEPS ? steps + 1 : steps; }
+};
+
 SBR_DEV int ring_k(const SbrPar& p, double t) {             // intervals since reset, from the running time
     double q = __builtin_fma(t - p.T_fill, p.inv_t_delta, 0.5);
     if (!(q >= 0.0)) q = 0.0;                                // also catches NaN
@@ -131,26 +156,6 @@ SBR_DEV int ring_k(const SbrPar& p, double t) {             // intervals since r
     return (int)q;
 }
 SBR_DEV int ring_wrap(int s) { return s >= SBR_KLA_HIST ? s - SBR_KLA_HIST : s; }       // for 0 <= s < 20
-// meta = steps*16384 + plan*64 + m1i*32 + idle*16 + status*2 + done.  `plan`: what cfg.scheme = 1 did in the last control
-// interval k_step ran for this env (step count + 128 if dissolved oxygen was held; 0 = none reported: scheme 0, a reset, an
-// import, a rollout) - SBR_C_PLAN of the public layout; it rides in this row so that reporting it moves no extra byte.  `idle`: the done call of k_step appended one more Kla than t accounts
-// for (Sim_idle's, :2578): the ring's oldest entry then sits one slot further than ring_k(t) says (k_export adds it; a reset,
-// an import or a rollout store the ring in plain order and clear the bit).  `m1i`: So[-1], Sno[-1] are x[8], x[9], their rows
-// are stale (set by an ordinary k_step call only; every other writer stores the rows and leaves it clear).
-#define SBR_META_M1I 32
-#define SBR_META_PLAN_SHIFT 6
-#define SBR_META_STEPS_SHIFT 14
-SBR_DEV double meta_pack(int steps, int status, bool done, bool idle = false, bool m1i = false, int plan = 0) {
-    return (double)((steps << SBR_META_STEPS_SHIFT) + ((plan & 0xff) << SBR_META_PLAN_SHIFT) + (m1i ? SBR_META_M1I : 0) + (idle ? 16 : 0) +
-                    status * 2 + (done ? 1 : 0));
-}
-SBR_DEV int meta_plan(double m) { return ((int)m >> SBR_META_PLAN_SHIFT) & 0xff; }
-SBR_DEV void meta_unpack(double m, int& steps, int& status, bool& done, bool& idle, bool& m1i) {
-    const int v = (int)m;
-    done = (v & 1) != 0; status = (v >> 1) & 7; idle = (v & 16) != 0; m1i = (v & SBR_META_M1I) != 0; steps = v >> SBR_META_STEPS_SHIFT;
-}
-SBR_DEV void meta_unpack(double m, int& steps, int& status, bool& done, bool& idle) { bool m1i; meta_unpack(m, steps, status, done, idle, m1i); }
-SBR_DEV void meta_unpack(double m, int& steps, int& status, bool& done) { bool idle; meta_unpack(m, steps, status, done, idle); }
 // the two rows k_step keeps next to the ring (SbrHistInc), from a history in logical order (oldest first, hist[9] = Kla[-1])
 SBR_DEV double hist_w8(const double (&hist)[SBR_KLA_HIST]) {
     double s = hist[1];
@@ -159,36 +164,54 @@ SBR_DEV double hist_w8(const double (&hist)[SBR_KLA_HIST]) {
     return s;
 }
 
-// Rows the step consumes BEFORE the integration.  So[-2], Sno[-2] only feed the derivative term (tauD != 0) and the
-// trajectory export's dcv_EC: read only then (need_m2, wave-uniform).
-// (k_step reads So[-1] / Sno[-1] from the plant when meta says they are implicit; here: the general form, m1i from meta)
-SBR_DEV void load_ctl_pre(const SbrBuf& b, int64_t i0, uint32_t l, bool need_m2, bool m1i, const double (&x)[SBR_NX], SbrCtl& c) {
-    c.t = CTRL(R_T);
-    c.so_m1 = x[8]; c.sno_m1 = x[9];
-    if (!m1i) { c.so_m1 = CTRL(R_SO_M1); c.sno_m1 = CTRL(R_SNO_M1); }
-    c.ie_do = CTRL(R_IE_DO); c.ie_ec = CTRL(R_IE_EC); c.ec_last = CTRL(R_EC_LAST);
-    c.so_m2 = need_m2 ? CTRL(R_SO_M2) : c.so_m1;
-    c.sno_m2 = need_m2 ? CTRL(R_SNO_M2) : c.sno_m1;
-    c.ec_prev = c.ec_last; c.u_do = 0.0; c.u_ec = 0.0;
-    c.n_new = 0; c.st_new = 0; c.span = 0.0; c.rows = 9; c.plans = 0;
-}
-// rows every step rewrites (the ring slot(s), return and meta are written by the caller); with_m1 = false leaves So[-1] and
-// Sno[-1] implicit (the caller then sets meta's m1i bit)
+// the rows every step rewrites; with_m1 = false leaves So[-1] and Sno[-1] implicit (the caller then sets meta's m1i bit)
 SBR_DEV void store_ctl(const SbrBuf& b, int64_t i0, uint32_t l, const SbrCtl& c, bool with_m1 = true) {
     st_out(&CTRL(R_T), c.t); st_out(&CTRL(R_SO_M2), c.so_m2); st_out(&CTRL(R_SNO_M2), c.sno_m2);
     if (with_m1) { st_out(&CTRL(R_SO_M1), c.so_m1); st_out(&CTRL(R_SNO_M1), c.sno_m1); }
     st_out(&CTRL(R_IE_DO), c.ie_do); st_out(&CTRL(R_IE_EC), c.ie_ec); st_out(&CTRL(R_EC_LAST), c.ec_last);
 }
-// whole history, logical order (oldest first), for the given interval count (per-lane slot: the general, slower form)
-SBR_DEV void load_ring(const SbrBuf& b, int64_t i0, uint32_t l, int k, double (&hist)[SBR_KLA_HIST]) {
-    const int kb = k % SBR_KLA_HIST;
+
+// An env's whole controller record.  k_step keeps its own sequence (one memory round trip, implicit m1 rows, ring appends);
+// every other kernel that reads or writes the record goes through load_record / store_record.  KSUM: whether the running sum
+// of Kla is read / written (only the operating-cost reward maintains it).
+struct SbrRecord {
+    SbrCtl c;                      // t, the two PIDs' memories and integrals, EC[-1], Kla[-1]; the per-call fields cleared
+    double hist[SBR_KLA_HIST];     // the Kla history in logical order (oldest first)
+    double ret, qw, ksum;
+    SbrMeta meta;
+};
+// The general form: So[-1] / Sno[-1] are the plant's x[8] / x[9] when meta's m1i bit says so, the ring's oldest entry sits at
+// ring_k(t) + idle.  Kla[-1] is taken from the ring, not from R_KLA_LAST.
+template <bool KSUM>
+SBR_DEV void load_record(const SbrPar& p, const SbrBuf& b, int64_t i0, uint32_t l, double x8, double x9, SbrRecord& r) {
+    SbrCtl& c = r.c;
+    r.meta = SbrMeta::unpack(CTRL(R_META));
+    c.t = CTRL(R_T);
+    c.so_m1 = x8; c.sno_m1 = x9;
+    if (!r.meta.m1i) { c.so_m1 = CTRL(R_SO_M1); c.sno_m1 = CTRL(R_SNO_M1); }
+    c.ie_do = CTRL(R_IE_DO); c.ie_ec = CTRL(R_IE_EC); c.ec_last = CTRL(R_EC_LAST);
+    c.so_m2 = CTRL(R_SO_M2); c.sno_m2 = CTRL(R_SNO_M2);
+    c.ec_prev = c.ec_last; c.u_do = 0.0; c.u_ec = 0.0;
+    c.n_new = 0; c.st_new = 0; c.span = 0.0; c.rows = 9; c.plans = 0;
+    const int kb = (ring_k(p, c.t) + (r.meta.idle ? 1 : 0)) % SBR_KLA_HIST;
 #pragma unroll
-    for (int j = 0; j < SBR_KLA_HIST; ++j) hist[j] = CTRL(R_RING0 + ring_wrap(kb + j));
+    for (int j = 0; j < SBR_KLA_HIST; ++j) r.hist[j] = CTRL(R_RING0 + ring_wrap(kb + j));
+    c.kla_last = r.hist[SBR_KLA_HIST - 1];
+    r.ret = CTRL(R_RET); r.qw = CTRL(R_QW); r.ksum = KSUM ? CTRL(R_KSUM) : 0.0;
 }
-SBR_DEV void store_ring(const SbrBuf& b, int64_t i0, uint32_t l, int k, const double (&hist)[SBR_KLA_HIST]) {
-    const int kb = k % SBR_KLA_HIST;
+// The explicit form, which every writer but k_step leaves: So[-1] / Sno[-1] in their rows, m1i and idle clear, the ring in
+// plain order for ring_k(t), R_KLA_LAST / R_W8 derived from it.  The eight rows of store_ctl go out written through, the rest
+// plainly.
+template <bool KSUM>
+SBR_DEV void store_record(const SbrPar& p, const SbrBuf& b, int64_t i0, uint32_t l, const SbrRecord& r) {
+    store_ctl(b, i0, l, r.c);
+    const int kb = ring_k(p, r.c.t) % SBR_KLA_HIST;
 #pragma unroll
-    for (int j = 0; j < SBR_KLA_HIST; ++j) CTRL(R_RING0 + ring_wrap(kb + j)) = hist[j];
+    for (int j = 0; j < SBR_KLA_HIST; ++j) CTRL(R_RING0 + ring_wrap(kb + j)) = r.hist[j];
+    CTRL(R_KLA_LAST) = r.hist[SBR_KLA_HIST - 1]; CTRL(R_W8) = hist_w8(r.hist);
+    CTRL(R_RET) = r.ret; CTRL(R_META) = SbrMeta::pack({r.meta.steps, r.meta.status, r.meta.done, false, false, r.meta.plan});
+    CTRL(R_QW) = r.qw;
+    if (KSUM) CTRL(R_KSUM) = r.ksum;
 }
 
 // public <-> internal translation (sbr_get_state / sbr_set_state / sbr_get_ctrl_row); only_row < 0 = all rows
@@ -196,25 +219,23 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_export(SbrPar p, SbrBuf b, double
     const uint32_t l = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * SBR_BLOCK, i = i0 + l;
     if (i >= b.n) return;
-    double v[SBR_NCTRL], hist[SBR_KLA_HIST];
-    int steps, status; bool done, idle, m1i;
-    const double t = CTRL(R_T);
-    meta_unpack(CTRL(R_META), steps, status, done, idle, m1i);
-    load_ring(b, i0, l, ring_k(p, t) + (idle ? 1 : 0), hist);
-    v[SBR_C_T] = t; v[SBR_C_SO_M1] = m1i ? XROW(8) : CTRL(R_SO_M1); v[SBR_C_SO_M2] = CTRL(R_SO_M2);
-    v[SBR_C_SNO_M1] = m1i ? XROW(9) : CTRL(R_SNO_M1); v[SBR_C_SNO_M2] = CTRL(R_SNO_M2);
-    v[SBR_C_IE_DO] = CTRL(R_IE_DO); v[SBR_C_IE_EC] = CTRL(R_IE_EC); v[SBR_C_EC_LAST] = CTRL(R_EC_LAST);
+    SbrRecord r;
+    load_record<true>(p, b, i0, l, XROW(8), XROW(9), r);
+    double v[SBR_NCTRL];
+    v[SBR_C_T] = r.c.t; v[SBR_C_SO_M1] = r.c.so_m1; v[SBR_C_SO_M2] = r.c.so_m2;
+    v[SBR_C_SNO_M1] = r.c.sno_m1; v[SBR_C_SNO_M2] = r.c.sno_m2;
+    v[SBR_C_IE_DO] = r.c.ie_do; v[SBR_C_IE_EC] = r.c.ie_ec; v[SBR_C_EC_LAST] = r.c.ec_last;
 #pragma unroll
-    for (int j = 0; j < SBR_KLA_HIST; ++j) v[SBR_C_KLA_HIST0 + j] = hist[j];
-    v[SBR_C_QW] = CTRL(R_QW); v[SBR_C_RETURN] = CTRL(R_RET); v[SBR_C_STEPS] = (double)steps;
-    v[SBR_C_DONE] = done ? 1.0 : 0.0; v[SBR_C_STATUS] = (double)status; v[SBR_C_KLA_SUM] = CTRL(R_KSUM);
-    v[SBR_C_PLAN] = (double)meta_plan(CTRL(R_META));
+    for (int j = 0; j < SBR_KLA_HIST; ++j) v[SBR_C_KLA_HIST0 + j] = r.hist[j];
+    v[SBR_C_QW] = r.qw; v[SBR_C_RETURN] = r.ret; v[SBR_C_STEPS] = (double)r.meta.steps;
+    v[SBR_C_DONE] = r.meta.done ? 1.0 : 0.0; v[SBR_C_STATUS] = (double)r.meta.status; v[SBR_C_KLA_SUM] = r.ksum;
+    v[SBR_C_PLAN] = (double)r.meta.plan;
     if (only_row >= 0) {
 #pragma unroll
-        for (int r = 0; r < SBR_NCTRL; ++r) if (r == only_row) out[i] = v[r];
+        for (int k = 0; k < SBR_NCTRL; ++k) if (k == only_row) out[i] = v[k];
     } else {
 #pragma unroll
-        for (int r = 0; r < SBR_NCTRL; ++r) out[(int64_t)r * b.n + i] = v[r];
+        for (int k = 0; k < SBR_NCTRL; ++k) out[(int64_t)k * b.n + i] = v[k];
     }
 }
 // makes implicit So[-1] / Sno[-1] explicit (sbr_set_state with a plant only)
@@ -222,10 +243,11 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_m1_explicit(SbrBuf b) {
     const uint32_t l = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * SBR_BLOCK;
     if (i0 + l >= b.n) return;
-    const int m = (int)CTRL(R_META);
-    if ((m & SBR_META_M1I) != 0) {
+    SbrMeta m = SbrMeta::unpack(CTRL(R_META));
+    if (m.m1i) {
         CTRL(R_SO_M1) = XROW(8); CTRL(R_SNO_M1) = XROW(9);
-        CTRL(R_META) = (double)(m & ~SBR_META_M1I);
+        m.m1i = false;
+        CTRL(R_META) = SbrMeta::pack(m);
     }
 }
 __global__ __launch_bounds__(SBR_BLOCK) void k_import(SbrPar p, SbrBuf b, const double* __restrict__ in) {
@@ -233,21 +255,19 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_import(SbrPar p, SbrBuf b, const 
     const int64_t i0 = (int64_t)blockIdx.x * SBR_BLOCK, i = i0 + l;
     if (i >= b.n) return;
 #define IN(r) in[(int64_t)(r) * b.n + i]
-    const double t = IN(SBR_C_T);
-    double hist[SBR_KLA_HIST];
+    SbrRecord r;
+    r.c.t = IN(SBR_C_T); r.c.so_m1 = IN(SBR_C_SO_M1); r.c.so_m2 = IN(SBR_C_SO_M2);
+    r.c.sno_m1 = IN(SBR_C_SNO_M1); r.c.sno_m2 = IN(SBR_C_SNO_M2);
+    r.c.ie_do = IN(SBR_C_IE_DO); r.c.ie_ec = IN(SBR_C_IE_EC); r.c.ec_last = IN(SBR_C_EC_LAST);
 #pragma unroll
-    for (int j = 0; j < SBR_KLA_HIST; ++j) hist[j] = IN(SBR_C_KLA_HIST0 + j);
-    CTRL(R_T) = t; CTRL(R_SO_M1) = IN(SBR_C_SO_M1); CTRL(R_SO_M2) = IN(SBR_C_SO_M2);
-    CTRL(R_SNO_M1) = IN(SBR_C_SNO_M1); CTRL(R_SNO_M2) = IN(SBR_C_SNO_M2);
-    CTRL(R_IE_DO) = IN(SBR_C_IE_DO); CTRL(R_IE_EC) = IN(SBR_C_IE_EC); CTRL(R_EC_LAST) = IN(SBR_C_EC_LAST);
-    store_ring(b, i0, l, ring_k(p, t), hist);
-    CTRL(R_KLA_LAST) = hist[SBR_KLA_HIST - 1]; CTRL(R_W8) = hist_w8(hist);
-    CTRL(R_QW) = IN(SBR_C_QW); CTRL(R_RET) = IN(SBR_C_RETURN); CTRL(R_KSUM) = IN(SBR_C_KLA_SUM);
+    for (int j = 0; j < SBR_KLA_HIST; ++j) r.hist[j] = IN(SBR_C_KLA_HIST0 + j);
+    r.qw = IN(SBR_C_QW); r.ret = IN(SBR_C_RETURN); r.ksum = IN(SBR_C_KLA_SUM);
     double st = IN(SBR_C_STEPS);
     st = st >= 0.0 ? (st < (double)SBR_MAX_STEPS ? st : (double)SBR_MAX_STEPS) : 0.0;
     double pl = IN(SBR_C_PLAN);
     pl = pl >= 0.0 ? (pl < 255.0 ? pl : 255.0) : 0.0;       // also catches NaN
-    CTRL(R_META) = meta_pack((int)st, (int)IN(SBR_C_STATUS) & 7, IN(SBR_C_DONE) != 0.0, false, false, (int)pl);
+    r.meta.steps = (int)st; r.meta.status = (int)IN(SBR_C_STATUS) & 7; r.meta.done = IN(SBR_C_DONE) != 0.0; r.meta.plan = (int)pl;
+    store_record<true>(p, b, i0, l, r);
 #undef IN
 }
 
@@ -351,8 +371,8 @@ __global__ __launch_bounds__(BLK) void k_reset(SbrPar p, SbrBuf b, const double*
     for (int j = 0; j < SBR_NX; ++j) { x[j] = x0[j]; INFL(j) = ld[j]; }
 
     // ---- fill phase, Sim_filling :1585-1654.  DO-PID at t_start == 0: ie = 0, dcv = 0, set-point 0
-    SbrCtl c;
-    double hist[SBR_KLA_HIST];
+    SbrRecord rec;
+    SbrCtl& c = rec.c;
     const double e = 0.0 - x0[8];
     double ie = 0.0;
     double kla = p.Kc_DO * e + p.KcI_DO * ie;
@@ -365,16 +385,14 @@ __global__ __launch_bounds__(BLK) void k_reset(SbrPar p, SbrBuf b, const double*
     c.ie_do = ie; c.ie_ec = 0.0; c.ec_last = 0.0; c.ec_prev = 0.0;
     c.u_do = 0.0; c.u_ec = 15.0;                                     // :212-213
 #pragma unroll
-    for (int j = 0; j < SBR_KLA_HIST; ++j) hist[j] = ((SBR_KLA_HIST - 1 - j) % 2 == 0) ? kla : 0.0;   // [0,k]*126, :323
+    for (int j = 0; j < SBR_KLA_HIST; ++j) rec.hist[j] = ((SBR_KLA_HIST - 1 - j) % 2 == 0) ? kla : 0.0;   // [0,k]*126, :323
     c.kla_last = kla;
+    rec.ret = 0.0; rec.qw = 0.0;
+    rec.meta.status = sbr_status_bits(p, x);
+    rec.ksum = 0.0;                                  // python's sum() over the list [0, k]*126, left to right
+    for (int j = 0; j < p.fill_rows / 2; ++j) rec.ksum = rec.ksum + kla;
     store_x(b, i0, l, x);
-    store_ctl(b, i0, l, c);
-    store_ring(b, i0, l, ring_k(p, c.t), hist);      // k = 0: logical order = slot order
-    CTRL(R_KLA_LAST) = hist[SBR_KLA_HIST - 1]; CTRL(R_W8) = hist_w8(hist);
-    CTRL(R_RET) = 0.0; CTRL(R_META) = meta_pack(0, sbr_status_bits(p, x), false); CTRL(R_QW) = 0.0;
-    double ksum = 0.0;                               // python's sum() over the list [0, k]*126, left to right
-    for (int j = 0; j < p.fill_rows / 2; ++j) ksum = ksum + kla;
-    CTRL(R_KSUM) = ksum;
+    store_record<true>(p, b, i0, l, rec);
     if (obs) {   // volume blend of influent and post-fill state, :346-361
         double xr[SBR_NX];
         const double rwv = sbr_rcp(qin + iv);
@@ -408,7 +426,9 @@ __global__ __launch_bounds__(BLK) void k_reset(SbrPar p, SbrBuf b, const double*
 #define SBR_PK_X6 3
 #define SBR_PK_KSUM (SBR_PK_X6 + SBR_NXD)
 #define SBR_NPARK 20
-#define SBR_NPARK_2W 32     // k_step<.., WAVES = 2>: + what the call keeps across the integration (SbrX6LdsT<true>)
+#define SBR_NPARK_2W 32     // k_step<.., WAVES = 2>: + the parked values (SbrPark, behind the six start values and the OCI sum)
+static_assert(SBR_PK_KSUM + 1 + PK_CALL_END <= SBR_NPARK_2W && SBR_PK_KSUM + 1 + PK_TERM_END <= SBR_NPARK_2W,
+              "the LDS region of the two-waves build is too small for its parked values");
 
 // One output row per lane (obs: 18 values, state: 15) -> the caller's row-major tensor.  A full wavefront owns 64
 // consecutive rows, i.e. ONE contiguous block of 64 x NV x sizeof(OutT) bytes (4608 B of float32 observations): the rows go
@@ -557,12 +577,11 @@ SBR_DEV void sbr_warm_kernarg_wait(uint32_t t) { asm volatile("s_waitcnt lgkmcnt
 // across the integration for it.  Off (b.trace == NULL, the default) this is one untaken scalar branch per interval.
 struct SbrTraceRec {
     const SbrBuf& b;
-    const double* meta_lds;       // the lane's parked steps/status/done word
+    const double* meta_lds;       // the lane's parked meta word
     int64_t env;                  // index of the lane's env in the handle
     SBR_DEV void pid(int iv, double e, double ie, double dcv) const {
         if (__builtin_expect(b.trace != nullptr, 0)) {
-            // meta = steps*16384 + plan*64 + m1i*32 + idle*16 + status*2 + done
-            const int64_t steps = (int64_t)((int)(*meta_lds) >> SBR_META_STEPS_SHIFT);
+            const int64_t steps = (int64_t)((int)(*meta_lds) >> SbrMeta::kStepsShift);
             if (env < b.n_trace && steps < b.trace_cap) {
                 double* rec = b.trace + (steps * SBR_NTRACE) * b.n_trace + env;
                 if (iv == 0) {
@@ -591,9 +610,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
     // transpose (64 float64 observation rows take 9216 B, float32 observation + state rows together 8448 B)
     constexpr bool PARK = WAVES == 2;
     constexpr int NSLOT = PARK ? SBR_NPARK_2W : SBR_NPARK;
-    // parked values: slots SBR_PK_X6 + SBR_NXD + 1 + j, j < 20 (13 per interval + 7 of the call; 19 around the terminal phases)
-    static_assert(!PARK || SBR_NPARK_2W >= SBR_PK_X6 + SBR_NXD + 1 + 20, "the LDS region of the two-waves build is too small for its parked values");
-    // ... and its upper bounds: static LDS is limited to 64 KiB per workgroup, and the two-waves build only pays while
+    // the upper bounds of the parking region: static LDS is limited to 64 KiB per workgroup, and the two-waves build only pays while
     // TWO of its workgroups fit the 160 KiB of a CU - one more __shared__ word would silently halve the residency
     static_assert(sizeof(double) * NSLOT * BLK <= 65536, "k_step's parking region exceeds the 64 KiB static LDS limit");
     static_assert(!PARK || 2 * sizeof(double) * NSLOT * BLK <= 160 * 1024, "two workgroups of the two-waves build must fit a CU's 160 KiB of LDS");
@@ -646,15 +663,14 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
     double t_obs = p.t_cycle, r = 0.0;
     bool dn = true;
     double xa6[SBR_NXD];
-    if (((int)meta0 & 1) == 0) {          // not done: a finished env waits for sbr_reset (the reference leaves resetting to the caller)
+    if (((int)meta0 & SbrMeta::kDone) == 0) {   // not done: a finished env waits for sbr_reset (the reference leaves resetting to the caller)
         double qw = 0.0;
-        int steps, status; bool was_done;
         SbrRewardParts rp;
         const double v0 = x[0], si0 = x[1], xi0 = x[3];
         // So[-1], Sno[-1]: the plant's own values after an ordinary step (meta's m1i bit); the first call after a reset, an import
         // or a rollout fetches the rows (a second, dependent load: once per episode)
         c.so_m1 = x[8]; c.sno_m1 = x[9];
-        const bool m1_rows = ((int)meta0 & SBR_META_M1I) == 0;
+        const bool m1_rows = ((int)meta0 & SbrMeta::kM1i) == 0;
         if (__builtin_amdgcn_ballot_w64(m1_rows) != 0ull) {
             if (m1_rows) { c.so_m1 = CTRL(R_SO_M1); c.sno_m1 = CTRL(R_SNO_M1); }
         }
@@ -662,15 +678,16 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         SBR_STAMP(2, false);
         const SbrTraceRec tr{b, my + SBR_PK_META * 64, i0 + l};
         if constexpr (PARK) {
-            x6.park(13, lv[0]); x6.park(14, lv[1]); x6.park(15, lv[2]); x6.park(16, kla_before); x6.park(17, v0); x6.park(18, si0);
-            x6.park(19, xi0);
+            x6.park(PK_CALL_LV0, lv[0]); x6.park(PK_CALL_LV1, lv[1]); x6.park(PK_CALL_LV2, lv[2]);
+            x6.park(PK_CALL_KLA_BEFORE, kla_before); x6.park(PK_CALL_V0, v0); x6.park(PK_CALL_SI0, si0); x6.park(PK_CALL_XI0, xi0);
         }
         sbr_run_intervals<SCH>(p, c, x, a0, a1, x6, tr);
         double kla_before_r = kla_before, v0_r = v0, si0_r = si0, xi0_r = xi0;
         if constexpr (PARK) {
             asm volatile("" : "+v"(l) : : "memory");  // the row addresses of the stores are formed again from here (not kept across the integration)
-            lv[0] = x6.unpark(13); lv[1] = x6.unpark(14); lv[2] = x6.unpark(15);
-            kla_before_r = x6.unpark(16); v0_r = x6.unpark(17); si0_r = x6.unpark(18); xi0_r = x6.unpark(19);
+            lv[0] = x6.unpark(PK_CALL_LV0); lv[1] = x6.unpark(PK_CALL_LV1); lv[2] = x6.unpark(PK_CALL_LV2);
+            kla_before_r = x6.unpark(PK_CALL_KLA_BEFORE); v0_r = x6.unpark(PK_CALL_V0); si0_r = x6.unpark(PK_CALL_SI0);
+            xi0_r = x6.unpark(PK_CALL_XI0);
         }
         SBR_STAMP(3, false);                  // PIDs + RK4 done
         SbrHistInc hs{my[SBR_PK_W8 * 64], kla_before_r, {lv[0], lv[1], lv[2]}, 0.0, false};
@@ -722,12 +739,13 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         }
         st_out(&CTRL(R_KLA_LAST), last_new); st_out(&CTRL(R_W8), w8_new);
         if (dn && p.terminal) CTRL(R_QW) = qw;
-        meta_unpack(my[SBR_PK_META * 64], steps, status, was_done);
+        const SbrMeta m = SbrMeta::unpack(my[SBR_PK_META * 64]);
+        const int steps = m.steps;
         st_out(&CTRL(R_RET), my[SBR_PK_RET * 64] + r);
         // the m1i bit ("So[-1] / Sno[-1] are x[8] / x[9]") is claimed only by a call that RAN an interval: a call with
         // n_new == 0 (t injected as NaN) writes nothing to the memories, so it leaves them where they were - rows stay rows
         const bool m1i_new = dn ? false : (c.n_new > 0 ? true : !m1_rows);
-        st_out(&CTRL(R_META), meta_pack(steps < SBR_MAX_STEPS ? steps + 1 : steps, status | c.st_new, dn, idle_pushed, m1i_new, c.plans & 0xff));
+        st_out(&CTRL(R_META), SbrMeta::pack({SbrMeta::next_steps(steps), m.status | c.st_new, dn, idle_pushed, m1i_new, c.plans & 0xff}));
         SBR_STAMP(10, false);                 // controller stores issued
         if (b.trace != nullptr && i0 + l < b.n_trace && (int64_t)steps < b.trace_cap) {     // trajectory export, off by default
             double* rec = b.trace + ((int64_t)steps * SBR_NTRACE) * b.n_trace + (i0 + l);
@@ -737,15 +755,11 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
             rec[SBR_TR_KLA * b.n_trace] = c.knew[c.n_new > 1 ? 1 : 0]; rec[SBR_TR_EC * b.n_trace] = c.ec_last;
             rec[SBR_TR_REWARD * b.n_trace] = r; rec[SBR_TR_DONE * b.n_trace] = dn ? 1.0 : 0.0;
             rec[SBR_TR_U_DO * b.n_trace] = c.u_do; rec[SBR_TR_U_EC * b.n_trace] = c.u_ec;
-            // (e_EC, ie_EC, dcv_EC of the interval(s): written by SbrTraceRec::pid as the PIDs ran)
-            // module_reward_EQIOCI.py:60-112: EQI2, and the cost terms over their maxima (Kla = 240, EC = 0.0005 throughout)
             const double ae2 = rp.ae * p.inv_ae_max, ec2 = rp.ec * p.inv_ec_max;
             rec[SBR_TR_R_EQI * b.n_trace] = rp.eqi2; rec[SBR_TR_R_OCI * b.n_trace] = ae2 + ec2;
             rec[SBR_TR_R_AE * b.n_trace] = ae2; rec[SBR_TR_R_EC * b.n_trace] = ec2;
-            // what rebuilding the sub-interval rows needs (sbr_eval_substeps): the intervals run and the first one's Kla / EC
             rec[SBR_TR_N_IV * b.n_trace] = (double)c.n_new; rec[SBR_TR_KLA_FIRST * b.n_trace] = c.knew[0];
             rec[SBR_TR_EC_FIRST * b.n_trace] = c.n_new > 1 ? c.ec_prev : c.ec_last;
-            // what cfg.scheme = 1 did (round 6): plan code of the call's last interval and of its first (equal when one ran)
             rec[SBR_TR_PLAN * b.n_trace] = (double)(c.plans & 0xff); rec[SBR_TR_PLAN_FIRST * b.n_trace] = (double)((c.plans >> 8) & 0xff);
         }
     } else {
@@ -796,8 +810,7 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout(SbrPar p, SbrBuf b
     const int64_t i0 = (int64_t)blockIdx.x * SBR_BLOCK, i = i0 + l;
     if (i >= b.n) return;
     const uint64_t gid = (uint64_t)(b.first_env_id + i);
-    double x[SBR_NX], xa6[SBR_NXD], hist[SBR_KLA_HIST];
-    SbrCtl c;
+    double x[SBR_NX], xa6[SBR_NXD];
     // x6 and the ten Kla values stay in registers.  With the terminal phases INSIDE the loop over the calls the kernel needed
     // 268 VGPRs and, capped at 256 for two waves per SIMD, spilled six loop invariants to 52 B of scratch per lane; parking x6 or
     // the history in LDS removed the spill and was 1 - 2 % slower.  Running settle / draw / idle once AFTER the loop (a finished
@@ -806,41 +819,34 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout(SbrPar p, SbrBuf b
     SbrX6Reg x6;
     SbrRewardParts rp;
     load_x(b, i0, l, x);
-    int steps, status; bool finished, idle_bit, m1i;
-    meta_unpack(CTRL(R_META), steps, status, finished, idle_bit, m1i);
-    load_ctl_pre(b, i0, l, true, m1i, x, c);
-    load_ring(b, i0, l, ring_k(p, c.t) + (idle_bit ? 1 : 0), hist);
-    c.kla_last = hist[SBR_KLA_HIST - 1];
-    double ret = CTRL(R_RET), qw = CTRL(R_QW), ksum = OCI ? CTRL(R_KSUM) : 0.0;
+    SbrRecord rec;
+    load_record<OCI>(p, b, i0, l, x[8], x[9], rec);
+    SbrCtl& c = rec.c;
+    SbrMeta& m = rec.meta;
     double acc = 0.0;
     bool terminal_due = false;        // the done call happened in this launch: its settle / draw / idle run once, after the loop
     for (int32_t s = 0; s < n_steps; ++s) {
         float a0, a1;
-        sbr_policy_action(p, policy_seed, gid, (uint32_t)steps, a0, a1);
+        sbr_policy_action(p, policy_seed, gid, (uint32_t)m.steps, a0, a1);
         if (actions_out) reinterpret_cast<float2*>(actions_out)[(int64_t)s * b.n + i] = make_float2(a0, a1);
-        if (finished) continue;
+        if (m.done) continue;
         double t_obs;
         bool dn;
         sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
         x6.get(xa6);
-        SbrHistReg hs{hist};
-        const double r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, qw, ksum, rp);
-        acc += r; ret += r; status |= c.st_new;
-        if (steps < SBR_MAX_STEPS) steps += 1;
-        if (dn) { finished = true; terminal_due = !OCI && p.terminal; }
+        SbrHistReg hs{rec.hist};
+        const double r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, rec.qw, rec.ksum, rp);
+        acc += r; rec.ret += r; m.status |= c.st_new;
+        m.steps = SbrMeta::next_steps(m.steps);
+        if (dn) { m.done = true; terminal_due = !OCI && p.terminal; }
     }
     if (terminal_due) {               // a finished lane skipped every later call, so c, x and hist are as the done call left them
-        SbrHistReg hs{hist};
-        qw = sbr_terminal<SCH>(p, c, hs, x);
+        SbrHistReg hs{rec.hist};
+        rec.qw = sbr_terminal<SCH>(p, c, hs, x);
     }
+    m.plan = 0;                       // a rollout reports no plan
     store_x(b, i0, l, x);
-    store_ctl(b, i0, l, c);
-    // the ring is addressed by the interval count recovered from t: store the logical history consistently with the final t
-    // (the idle phase's extra Kla does not advance t; k_export reads with the same rule)
-    store_ring(b, i0, l, ring_k(p, c.t), hist);
-    CTRL(R_KLA_LAST) = hist[SBR_KLA_HIST - 1]; CTRL(R_W8) = hist_w8(hist);
-    CTRL(R_RET) = ret; CTRL(R_META) = meta_pack(steps, status, finished); CTRL(R_QW) = qw;
-    if (OCI) CTRL(R_KSUM) = ksum;                     // like k_step: only this reward maintains the row
+    store_record<OCI>(p, b, i0, l, rec);
     if (returns) returns[i] = acc;
 }
 // ------------------------------------------------------------------------------------------- per-cycle env (SBR-v2)
@@ -873,7 +879,7 @@ __global__ __launch_bounds__(SBR_RESET_BLOCK) void k_cycle_reset(SbrPar p, SbrBu
 #pragma unroll
     for (int j = 0; j < SBR_NX; ++j) INFL(j) = ld[j];
     CTRL(R_T) = 0.0; CTRL(R_RET) = 0.0; CTRL(R_QW) = 0.0;
-    CTRL(R_META) = meta_pack(0, sbr_status_bits(p, x0), true);       // inert for sbr_step: this handle runs whole cycles
+    CTRL(R_META) = SbrMeta::pack({0, sbr_status_bits(p, x0), true});       // inert for sbr_step: this handle runs whole cycles
     if (obs) {
         const double cod = (x0[1] + ld[1]) + (x0[2] + ld[2]) + (x0[3] + ld[3]) + (x0[4] + ld[4]) + (x0[5] + ld[5]) +
                            (x0[6] + ld[6]) + (x0[7] + ld[7]);
@@ -899,7 +905,7 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_cycle(SbrPar p, SbrBuf b, 
                                    diag ? diag + i * SBR_NCYC_DIAG : nullptr, 1);
     store_x(b, i0, l, x);
     CTRL(R_RET) = CTRL(R_RET) + r; CTRL(R_T) = p.t_cycle;
-    CTRL(R_META) = meta_pack(1, st0 | sbr_status_bits(p, x), true);
+    CTRL(R_META) = SbrMeta::pack({1, st0 | sbr_status_bits(p, x), true});
     if (obs) { obs[i * 3 + 0] = (OutT)o3[0]; obs[i * 3 + 1] = (OutT)o3[1]; obs[i * 3 + 2] = (OutT)o3[2]; }
     if (reward) reward[i] = (OutT)r;
 }
@@ -1324,10 +1330,10 @@ int sbr_create(int64_t n_envs, int device_id, int64_t first_env_id, const sbr_co
     CREATE_TRY(hipMemset(e->buf.x, 0, SBR_NX * nb));
     CREATE_TRY(hipMemset(e->buf.ctrl, 0, R_NROWS * nb));
     CREATE_TRY(hipMemset(e->buf.infl, 0, SBR_NX * nb));
-    // an env is unusable until its first reset: mark everything done so that step() is a no-op until then
-    // (meta = steps*16384 + plan*64 + m1i*32 + idle*16 + status*2 + done  =>  1.0 = "done"); filled on the device, no host
-    // staging buffer
-    hipLaunchKernelGGL(k_fill, grid_for(n_envs), dim3(SBR_BLOCK), 0, nullptr, e->buf.ctrl + (size_t)R_META * n_envs, n_envs, 1.0);
+    // an env is unusable until its first reset: mark everything done so that step() is a no-op until then; filled on the
+    // device, no host staging buffer
+    hipLaunchKernelGGL(k_fill, grid_for(n_envs), dim3(SBR_BLOCK), 0, nullptr, e->buf.ctrl + (size_t)R_META * n_envs, n_envs,
+                       SbrMeta::pack({0, 0, true}));
     CREATE_TRY(hipGetLastError());
     CREATE_TRY(hipDeviceSynchronize());
     CREATE_TRY(hipEventCreate(&e->ev0));

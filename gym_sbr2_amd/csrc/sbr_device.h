@@ -608,11 +608,24 @@ struct SbrRewardParts { double eqi2, ae, ec; };
 SBR_DEV void sbr_take6(const double (&x)[SBR_NX], double (&x6)[SBR_NXD]) {
     x6[0] = x[2]; x6[1] = x[5]; x6[2] = x[6]; x6[3] = x[8]; x6[4] = x[9]; x6[5] = x[10];
 }
+// Park slots of the two-waves build of k_step (SbrX6LdsT<true>::park), counted from the first slot behind the six start values
+// and the OCI sum.  Three groups: what one interval keeps across its step loop (sbr_interval), what the call keeps across all of
+// its intervals (k_step), and what the done call keeps across the terminal phases (sbr_finish_step).  The first two are live at
+// the same time and must not overlap; k_step takes its values back before sbr_finish_step, so the third reuses both.
+enum SbrPark {
+    PK_IV_T1 = 0, PK_IV_SO_M1, PK_IV_SNO_M1, PK_IV_IE_DO, PK_IV_IE_EC, PK_IV_EC_LAST, PK_IV_EC, PK_IV_U_DO, PK_IV_U_EC, PK_IV_KLA,
+    PK_IV_KNEW0, PK_IV_SPAN, PK_IV_SMALL, PK_IV_END,
+    PK_CALL_LV0 = PK_IV_END, PK_CALL_LV1, PK_CALL_LV2, PK_CALL_KLA_BEFORE, PK_CALL_V0, PK_CALL_SI0, PK_CALL_XI0, PK_CALL_END,
+    PK_TERM_R = 0, PK_TERM_EQI2, PK_TERM_AE, PK_TERM_EC, PK_TERM_T, PK_TERM_SO_M1, PK_TERM_SO_M2, PK_TERM_SNO_M1, PK_TERM_SNO_M2,
+    PK_TERM_IE_EC, PK_TERM_EC_LAST, PK_TERM_EC_PREV, PK_TERM_U_EC, PK_TERM_KNEW0, PK_TERM_KNEW1, PK_TERM_SPAN, PK_TERM_SMALL,
+    PK_TERM_SNH_EFF, PK_TERM_KSUM, PK_TERM_END
+};
+static_assert(PK_IV_END <= PK_CALL_LV0, "the interval's parked values must not overlap the call's");
 // where the start values of an interval are parked while the RK4 loop runs: registers, or this lane's LDS slots
 struct SbrX6Reg {
     static constexpr bool kPark = false;
-    SBR_DEV void park(int, double) const {}
-    SBR_DEV double unpark(int) const { return 0.0; }
+    SBR_DEV void park(SbrPark, double) const {}
+    SBR_DEV double unpark(SbrPark) const { return 0.0; }
     double v[SBR_NXD];
     SBR_DEV void put(const double (&x)[SBR_NX]) { sbr_take6(x, v); }
     SBR_DEV void get(double (&o)[SBR_NXD]) const {
@@ -625,8 +638,8 @@ struct SbrX6LdsT {         // slot j of the lane lives at base[j * 64] inside it
     // PARK (the two-waves-per-SIMD build of k_step): what the call keeps across the integration goes to the lane's slots behind
     // the six start values (and the OCI sum) while the step loop runs, so that the loop has the registers
     static constexpr bool kPark = PARK;
-    SBR_DEV void park(int j, double v) const { base[(SBR_NXD + 1 + j) * 64] = v; }
-    SBR_DEV double unpark(int j) const { return base[(SBR_NXD + 1 + j) * 64]; }
+    SBR_DEV void park(SbrPark j, double v) const { base[(SBR_NXD + 1 + j) * 64] = v; }
+    SBR_DEV double unpark(SbrPark j) const { return base[(SBR_NXD + 1 + j) * 64]; }
     double* base;
     SBR_DEV void put(const double (&x)[SBR_NX]) {
         base[0 * 64] = x[2]; base[1 * 64] = x[5]; base[2 * 64] = x[6]; base[3 * 64] = x[8]; base[4 * 64] = x[9];
@@ -637,7 +650,6 @@ struct SbrX6LdsT {         // slot j of the lane lives at base[j * 64] inside it
         for (int j = 0; j < SBR_NXD; ++j) o[j] = base[j * 64];
     }
 };
-using SbrX6Lds = SbrX6LdsT<false>;
 
 // the small integers of SbrCtl as ONE exactly representable double (the parked build of k_step keeps them in an LDS slot):
 // rows (<= 10) | st_new (< 8) << 4 | n_new (<= 2) << 7 | plans (16 bits) << 9
@@ -720,10 +732,10 @@ SBR_DEV void sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& x
     // the controller state - in registers while the step loop runs: 13 values go to the lane's LDS slots and come back
     double t1r = t1, klar = kla, ecr = ec, spanr = span;
     if constexpr (X6::kPark) {
-        xs6.park(0, t1); xs6.park(1, c.so_m1); xs6.park(2, c.sno_m1); xs6.park(3, c.ie_do); xs6.park(4, c.ie_ec);
-        xs6.park(5, c.ec_last); xs6.park(6, ec); xs6.park(7, c.u_do); xs6.park(8, c.u_ec); xs6.park(9, kla);
-        xs6.park(10, c.knew[0]); xs6.park(11, span);
-        xs6.park(12, sbr_pack_small(c));                  // rows, status bits, interval count, plans: small integers, exact
+        xs6.park(PK_IV_T1, t1); xs6.park(PK_IV_SO_M1, c.so_m1); xs6.park(PK_IV_SNO_M1, c.sno_m1); xs6.park(PK_IV_IE_DO, c.ie_do);
+        xs6.park(PK_IV_IE_EC, c.ie_ec); xs6.park(PK_IV_EC_LAST, c.ec_last); xs6.park(PK_IV_EC, ec); xs6.park(PK_IV_U_DO, c.u_do);
+        xs6.park(PK_IV_U_EC, c.u_ec); xs6.park(PK_IV_KLA, kla); xs6.park(PK_IV_KNEW0, c.knew[0]); xs6.park(PK_IV_SPAN, span);
+        xs6.park(PK_IV_SMALL, sbr_pack_small(c));         // rows, status bits, interval count, plans: small integers, exact
         asm volatile("" ::: "memory");
     }
     int plan = 0;
@@ -737,11 +749,12 @@ SBR_DEV void sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& x
     }
     if constexpr (X6::kPark) {
         asm volatile("" ::: "memory");
-        t1r = xs6.unpark(0); klar = xs6.unpark(9); ecr = xs6.unpark(6); spanr = xs6.unpark(11);
-        sbr_unpack_small(xs6.unpark(12), c);
-        c.knew[0] = xs6.unpark(10);
-        c.so_m1 = xs6.unpark(1); c.sno_m1 = xs6.unpark(2); c.ie_do = xs6.unpark(3); c.ie_ec = xs6.unpark(4);
-        c.ec_last = xs6.unpark(5); c.u_do = xs6.unpark(7); c.u_ec = xs6.unpark(8);
+        t1r = xs6.unpark(PK_IV_T1); klar = xs6.unpark(PK_IV_KLA); ecr = xs6.unpark(PK_IV_EC); spanr = xs6.unpark(PK_IV_SPAN);
+        sbr_unpack_small(xs6.unpark(PK_IV_SMALL), c);
+        c.knew[0] = xs6.unpark(PK_IV_KNEW0);
+        c.so_m1 = xs6.unpark(PK_IV_SO_M1); c.sno_m1 = xs6.unpark(PK_IV_SNO_M1); c.ie_do = xs6.unpark(PK_IV_IE_DO);
+        c.ie_ec = xs6.unpark(PK_IV_IE_EC); c.ec_last = xs6.unpark(PK_IV_EC_LAST); c.u_do = xs6.unpark(PK_IV_U_DO);
+        c.u_ec = xs6.unpark(PK_IV_U_EC);
     }
     if (c.n_new == 0) c.knew[0] = klar; else c.knew[1] = klar;    // n_new <= 2, see SbrCtl
     c.plans = c.n_new == 0 ? (plan | (plan << 8)) : ((c.plans & 0xff00) | plan);
@@ -1054,21 +1067,24 @@ SBR_DEV double sbr_finish_step(const SbrPar& p, SbrCtl& c, H& hs, double (&x)[SB
                 // the two-waves-per-SIMD build: nothing of the call is kept in registers across the idle phase's step loop
                 SbrX6LdsT<true> q = *pk;
                 q.put(x);                            // the caller fetches xa6 after this function
-                q.park(0, r); q.park(1, rp.eqi2); q.park(2, rp.ae); q.park(3, rp.ec); q.park(4, c.t); q.park(5, c.so_m1);
-                q.park(6, c.so_m2); q.park(7, c.sno_m1); q.park(8, c.sno_m2); q.park(9, c.ie_ec); q.park(10, c.ec_last);
-                q.park(11, c.ec_prev); q.park(12, c.u_ec); q.park(13, c.knew[0]); q.park(14, c.knew[1]); q.park(15, c.span);
-                q.park(16, sbr_pack_small(c)); q.park(17, snh_eff); q.park(18, ksum);
+                q.park(PK_TERM_R, r); q.park(PK_TERM_EQI2, rp.eqi2); q.park(PK_TERM_AE, rp.ae); q.park(PK_TERM_EC, rp.ec);
+                q.park(PK_TERM_T, c.t); q.park(PK_TERM_SO_M1, c.so_m1); q.park(PK_TERM_SO_M2, c.so_m2);
+                q.park(PK_TERM_SNO_M1, c.sno_m1); q.park(PK_TERM_SNO_M2, c.sno_m2); q.park(PK_TERM_IE_EC, c.ie_ec);
+                q.park(PK_TERM_EC_LAST, c.ec_last); q.park(PK_TERM_EC_PREV, c.ec_prev); q.park(PK_TERM_U_EC, c.u_ec);
+                q.park(PK_TERM_KNEW0, c.knew[0]); q.park(PK_TERM_KNEW1, c.knew[1]); q.park(PK_TERM_SPAN, c.span);
+                q.park(PK_TERM_SMALL, sbr_pack_small(c)); q.park(PK_TERM_SNH_EFF, snh_eff); q.park(PK_TERM_KSUM, ksum);
                 asm volatile("" ::: "memory");
                 qw = sbr_terminal<SCH>(p, c, hs, x);
                 asm volatile("" ::: "memory");
-                r = q.unpark(0); rp.eqi2 = q.unpark(1); rp.ae = q.unpark(2); rp.ec = q.unpark(3); c.t = q.unpark(4);
-                c.so_m1 = q.unpark(5); c.so_m2 = q.unpark(6); c.sno_m1 = q.unpark(7); c.sno_m2 = q.unpark(8);
-                c.ie_ec = q.unpark(9); c.ec_last = q.unpark(10); c.ec_prev = q.unpark(11); c.u_ec = q.unpark(12);
-                c.knew[0] = q.unpark(13); c.knew[1] = q.unpark(14); c.span = q.unpark(15);
-                sbr_unpack_small(q.unpark(16), c);
+                r = q.unpark(PK_TERM_R); rp.eqi2 = q.unpark(PK_TERM_EQI2); rp.ae = q.unpark(PK_TERM_AE); rp.ec = q.unpark(PK_TERM_EC);
+                c.t = q.unpark(PK_TERM_T); c.so_m1 = q.unpark(PK_TERM_SO_M1); c.so_m2 = q.unpark(PK_TERM_SO_M2);
+                c.sno_m1 = q.unpark(PK_TERM_SNO_M1); c.sno_m2 = q.unpark(PK_TERM_SNO_M2); c.ie_ec = q.unpark(PK_TERM_IE_EC);
+                c.ec_last = q.unpark(PK_TERM_EC_LAST); c.ec_prev = q.unpark(PK_TERM_EC_PREV); c.u_ec = q.unpark(PK_TERM_U_EC);
+                c.knew[0] = q.unpark(PK_TERM_KNEW0); c.knew[1] = q.unpark(PK_TERM_KNEW1); c.span = q.unpark(PK_TERM_SPAN);
+                sbr_unpack_small(q.unpark(PK_TERM_SMALL), c);
                 if (OCI) {
-                    ksum = q.unpark(18) + c.kla_last;
-                    r = sbr_reward_oci(p, 2, c.kla_last, ksum, qw, q.unpark(17));
+                    ksum = q.unpark(PK_TERM_KSUM) + c.kla_last;
+                    r = sbr_reward_oci(p, 2, c.kla_last, ksum, qw, q.unpark(PK_TERM_SNH_EFF));
                 }
                 t_obs = p.t_cycle;
                 return r;
