@@ -1038,6 +1038,9 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_normals(SbrBuf b, uint64_t seed, 
 }
 
 // =========================================================================================== host / C ABI
+#include <memory>
+#include <type_traits>
+
 struct sbr_env {
     int64_t n = 0;
     int device = 0;
@@ -1058,11 +1061,15 @@ static int fail(sbr_env* e, int code, const std::string& msg) {
     if (e) e->err = msg; else g_create_err = msg;
     return code;
 }
-#define HIP_TRY(e, call)                                                                              \
-    do {                                                                                              \
-        hipError_t _s = (call);                                                                       \
-        if (_s != hipSuccess)                                                                         \
-            return fail(e, SBR_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s));           \
+// A failed HIP call.  Only sbr_create passes no handle (the one it is building is not the caller's yet), and only there does
+// running out of device memory have a code of its own.
+static int hip_fail(sbr_env* e, hipError_t s, const char* call) {
+    return fail(e, !e && s == hipErrorOutOfMemory ? SBR_ERR_ALLOC : SBR_ERR_HIP, std::string(call) + ": " + hipGetErrorString(s));
+}
+#define HIP_TRY(e, call)                                          \
+    do {                                                          \
+        hipError_t _s = (call);                                   \
+        if (_s != hipSuccess) return hip_fail(e, _s, #call);      \
     } while (0)
 
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + SBR_BLOCK - 1) / SBR_BLOCK)); }
@@ -1082,6 +1089,15 @@ struct DeviceGuard {
 #define ON_DEVICE(e)                      \
     DeviceGuard _guard((e)->device);      \
     HIP_TRY(e, _guard.status)
+// The frame of an entry point that only launches kernels, behind its own argument check: launch() runs on the handle's device
+// and the launch status is collected once behind it.  (Entry points that copy or wait check each call where it is made:
+// ON_DEVICE, then HIP_TRY per call.)
+template <typename Launch> static int launched(sbr_env* e, Launch&& launch) {
+    ON_DEVICE(e);
+    launch();
+    HIP_TRY(e, hipGetLastError());
+    return SBR_OK;
+}
 
 // smallest double s with (int)(s / dt) >= rows, i.e. whose IEEE quotient by dt reaches rows: start at rows*dt and step
 // through the neighbouring doubles (the quotient is monotonic in s; a handful of steps at most)
@@ -1181,35 +1197,60 @@ template <typename T> using ResetFn = decltype(&k_reset<T, false>);
 template <typename T, int BLK> constexpr ResetFn<T> kReset[2] = {k_reset<T, false, BLK>, k_reset<T, true, BLK>};
 template <typename T> constexpr ResetFn<T> kCycleReset[2] = {k_cycle_reset<T, false>, k_cycle_reset<T, true>};
 
-template <typename OutT, typename ActT, bool OCI, int SCH>
-static void launch_step_k(sbr_env* e, const void* action, void* obs, void* state, void* reward, uint8_t* done,
-                          hipStream_t st) {
-    const int blk = step_block(e);
-    const uint32_t flags = ((e->par.KcD_DO != 0.0 || e->par.KcD_EC != 0.0 || e->buf.trace != nullptr) ? SBR_KF_NEED_M2 : 0u) |
-                           (blk == 256 ? SBR_KF_STAGGER : 0u);
-    // scheme 0 has no two-waves build (step_waves is 1 for it)
-    auto fn = k_step<OutT, ActT, 64, OCI, SCH>;
-    if (blk == 256) fn = step_waves(e) == 2 ? k_step<OutT, ActT, 256, OCI, SCH, SCH == 1 ? 2 : 1> : k_step<OutT, ActT, 256, OCI, SCH>;
-    hipLaunchKernelGGL(fn, dim3((unsigned)((e->n + blk - 1) / blk)), dim3(blk), 0, st, e->buf.x, e->buf.ctrl, e->buf.n,
-                       (const ActT*)action, flags, (OutT*)obs, (OutT*)state, (OutT*)reward, done, e->par, e->buf);
-}
-template <typename OutT, typename ActT>
-static void launch_step(sbr_env* e, const void* action, void* obs, void* state, void* reward, uint8_t* done,
-                        hipStream_t st) {
-    const bool oci = e->cfg.reward_kind == 2, b5 = e->cfg.scheme == 1;      // one instantiation per reward family and scheme
-    if (oci) { if (b5) launch_step_k<OutT, ActT, true, 1>(e, action, obs, state, reward, done, st); else launch_step_k<OutT, ActT, true, 0>(e, action, obs, state, reward, done, st); }
-    else { if (b5) launch_step_k<OutT, ActT, false, 1>(e, action, obs, state, reward, done, st); else launch_step_k<OutT, ActT, false, 0>(e, action, obs, state, reward, done, st); }
+// The handle's run-time choices as template arguments.  This is the only place that turns one into the other: f is called with
+// a Choice that names the output and action types, whether the reward is the operating cost (reward_kind 2) and the scheme.
+// A launch site names its kernel once, with the members of the Choice it needs.  Which WAVES builds of a kernel exist stays
+// with the launch site: a kernel is instantiated wherever its name is spelled, taken or not.
+template <typename OutT_, typename ActT_, bool OCI_, int SCH_>
+struct Choice {
+    using OutT = OutT_;
+    using ActT = ActT_;
+    static constexpr bool OCI = OCI_;
+    static constexpr int SCH = SCH_;
+};
+template <typename F> static void either(bool c, F&& f) { if (c) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> static void dispatch(const sbr_env* e, F&& f) {
+    either(e->cfg.out_f64, [&](auto o64) { either(e->cfg.act_f64, [&](auto a64) {
+        either(e->cfg.reward_kind == 2, [&](auto oci) { either(e->cfg.scheme == 1, [&](auto b5) {
+            f(Choice<std::conditional_t<decltype(o64)::value, double, float>, std::conditional_t<decltype(a64)::value, double, float>,
+                     decltype(oci)::value, decltype(b5)::value ? 1 : 0>{});
+        }); });
+    }); });
 }
 
-template <typename T, typename A>
-static void launch_cycle(sbr_env* e, const void* action, void* obs, void* reward, double* diag, hipStream_t st) {
-    const auto fn = e->cfg.scheme == 1 ? (fused_waves(e) == 1 ? k_cycle<T, A, 1, 1> : k_cycle<T, A, 1, 2>) : k_cycle<T, A, 0, 2>;
-    hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, st, e->par, e->buf, (const A*)action, (T*)obs, (T*)reward, diag);
-}
-template <bool OCI>
-static void launch_rollout(sbr_env* e, int32_t n_steps, uint64_t policy_seed, double* returns, float* actions_out, hipStream_t st) {
-    const auto fn = e->cfg.scheme == 1 ? (fused_waves(e) == 1 ? k_rollout<OCI, 1, 1> : k_rollout<OCI, 1, 2>) : k_rollout<OCI, 0, 2>;
-    hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, st, e->par, e->buf, n_steps, policy_seed, returns, actions_out);
+// the fused kernels (k_cycle, k_rollout): scheme 0 has no one-wave build (fused_waves is 2 for it)
+template <int SCH> constexpr int kFusedOneWave = SCH == 1 ? 1 : 2;
+
+// What sbr_create has to say about a config; empty if it is valid.  Every check is evaluated and the LAST failing one is reported.
+static std::string config_error(const sbr_config& c) {
+    std::string bad;
+    if (c.substeps < 1 || c.substeps > 10000) bad = "substeps out of range";
+    if (c.scheme < 0 || c.scheme > 1) bad = "scheme must be 0 (RK4 x substeps) or 1 (adaptive Butcher-5)";
+    if (c.reserved_ != 0) bad = "reserved_ must be 0 (a caller that leaves it uninitialised could not be told from one using a later meaning)";
+    if (!(c.Koa > 0 && c.Koa < 1e300)) bad = "Koa must be positive";
+    if (c.reward_kind < 0 || c.reward_kind > 2) bad = "reward_kind must be 0 (EQI/OCI), 1 (G2ANET) or 2 (operating cost)";
+    if (!(c.dt > 0) || !(c.t_delta > 0)) bad = "dt and t_delta must be positive";
+    else {
+        const int rows = (int)(c.t_delta / c.dt + 0.5);
+        if (rows != 10) bad = "t_delta must be 10*dt (the reward's Kla look-back is 9 intervals)";
+    }
+    if (!(c.T_fill > 0) || (int)(c.T_fill / c.dt) < 1) bad = "T_fill/dt must be >= 1";
+    // every reaction phase must be longer than one control interval, so that a call runs at most two intervals
+    // (the reference's schedule: phases of 46, 190, 171 and 1 intervals; the last phase is open-ended)
+    if (!(c.T3_0 - c.T_fill > c.t_delta) || !(c.T3_end - c.T3_0 > c.t_delta) || !(c.T4_end - c.T3_end > c.t_delta))
+        bad = "phases 2, 3 and 4 must each be longer than t_delta";
+    if (!(c.tauI_DO != 0) || !(c.tauI_EC != 0) || !(c.cyc_tauI != 0) || !(c.cyc_dt > 0)) bad = "tauI must be non-zero, cyc_dt positive";
+    // the rate constants that are folded into the Monod denominators (sbr_rates) must be positive and finite
+    if (!(c.muH > 0 && c.muH < 1e300) || !(c.muA > 0 && c.muA < 1e300) || !(c.kh > 0 && c.kh < 1e300) ||
+        !(c.eta_g > 0 && c.eta_g < 1e300) || !(c.bH > 0 && c.bH < 1e300) || !(c.Ya > 0 && c.Ya < 1e300) ||
+        !(c.Koh > 0 && c.Koh < 1e300))
+        bad = "muH, muA, kh, eta_g, Koh, bH and Ya must be positive";
+    // the dosing integrator expands 1/s, s = V/V0, to third order in s - 1 <= EC_max t_delta / V (sbr_rk4_dose): 7e-7 with
+    // the reference's EC_max; refuse configurations in which the truncation (s - 1)^4 would reach 1e-16
+    if (!(c.IV > 0) || !(c.WV > 0) || !(c.EC_max * c.t_delta <= 1e-4 * (c.IV < c.WV ? c.IV : c.WV)))
+        bad = "EC_max * t_delta must be below 1e-4 of the reactor volume (IV, WV > 0)";
+    for (int k = 0; k < 8; ++k) if (!(c.t_ratio[k] > 0)) bad = "t_ratio entries must be positive";
+    return bad;
 }
 
 extern "C" {
@@ -1268,88 +1309,49 @@ int sbr_create(int64_t n_envs, int device_id, int64_t first_env_id, const sbr_co
     if (ndev <= 0)
         return fail(nullptr, SBR_ERR_NO_DEVICE, "sbr_create: no HIP device visible - this library has no CPU path");
     if (device_id < 0 || device_id >= ndev) return fail(nullptr, SBR_ERR_INVALID, "sbr_create: bad device_id");
-    sbr_env* e = new (std::nothrow) sbr_env();
+    sbr_config c;
+    if (cfg) c = *cfg; else sbr_default_config(&c);
+    const std::string bad = config_error(c);
+    if (!bad.empty()) return fail(nullptr, SBR_ERR_INVALID, "sbr_create: " + bad);
+    // the handle is this function's until the last line: every early return below destroys it with whatever it holds by then,
+    // and reports to the calling thread (HIP_TRY(nullptr, ...), sbr_last_error(NULL))
+    struct Destroy { void operator()(sbr_env* p) const { sbr_destroy(p); } };
+    std::unique_ptr<sbr_env, Destroy> e(new (std::nothrow) sbr_env());
     if (!e) return fail(nullptr, SBR_ERR_ALLOC, "sbr_create: out of host memory");
-    e->n = n_envs; e->device = device_id; e->first_env_id = first_env_id;
-    if (cfg) e->cfg = *cfg; else sbr_default_config(&e->cfg);
-    const sbr_config& c = e->cfg;
-    std::string bad;
-    if (c.substeps < 1 || c.substeps > 10000) bad = "substeps out of range";
-    if (c.scheme < 0 || c.scheme > 1) bad = "scheme must be 0 (RK4 x substeps) or 1 (adaptive Butcher-5)";
-    if (c.reserved_ != 0) bad = "reserved_ must be 0 (a caller that leaves it uninitialised could not be told from one using a later meaning)";
-    if (!(c.Koa > 0 && c.Koa < 1e300)) bad = "Koa must be positive";
-    if (c.reward_kind < 0 || c.reward_kind > 2) bad = "reward_kind must be 0 (EQI/OCI), 1 (G2ANET) or 2 (operating cost)";
-    if (!(c.dt > 0) || !(c.t_delta > 0)) bad = "dt and t_delta must be positive";
-    else {
-        const int rows = (int)(c.t_delta / c.dt + 0.5);
-        if (rows != 10) bad = "t_delta must be 10*dt (the reward's Kla look-back is 9 intervals)";
-    }
-    if (!(c.T_fill > 0) || (int)(c.T_fill / c.dt) < 1) bad = "T_fill/dt must be >= 1";
-    // every reaction phase must be longer than one control interval, so that a call runs at most two intervals
-    // (the reference's schedule: phases of 46, 190, 171 and 1 intervals; the last phase is open-ended)
-    if (!(c.T3_0 - c.T_fill > c.t_delta) || !(c.T3_end - c.T3_0 > c.t_delta) || !(c.T4_end - c.T3_end > c.t_delta))
-        bad = "phases 2, 3 and 4 must each be longer than t_delta";
-    if (!(c.tauI_DO != 0) || !(c.tauI_EC != 0) || !(c.cyc_tauI != 0) || !(c.cyc_dt > 0)) bad = "tauI must be non-zero, cyc_dt positive";
-    // the rate constants that are folded into the Monod denominators (sbr_rates) must be positive and finite
-    if (!(c.muH > 0 && c.muH < 1e300) || !(c.muA > 0 && c.muA < 1e300) || !(c.kh > 0 && c.kh < 1e300) ||
-        !(c.eta_g > 0 && c.eta_g < 1e300) || !(c.bH > 0 && c.bH < 1e300) || !(c.Ya > 0 && c.Ya < 1e300) ||
-        !(c.Koh > 0 && c.Koh < 1e300))
-        bad = "muH, muA, kh, eta_g, Koh, bH and Ya must be positive";
-    if (c.substeps > (1 << 20)) bad = "substeps out of range";
-    // the dosing integrator expands 1/s, s = V/V0, to third order in s - 1 <= EC_max t_delta / V (sbr_rk4_dose): 7e-7 with
-    // the reference's EC_max; refuse configurations in which the truncation (s - 1)^4 would reach 1e-16
-    if (!(c.IV > 0) || !(c.WV > 0) || !(c.EC_max * c.t_delta <= 1e-4 * (c.IV < c.WV ? c.IV : c.WV)))
-        bad = "EC_max * t_delta must be below 1e-4 of the reactor volume (IV, WV > 0)";
-    for (int k = 0; k < 8; ++k) if (!(c.t_ratio[k] > 0)) bad = "t_ratio entries must be positive";
-    if (!bad.empty()) { delete e; return fail(nullptr, SBR_ERR_INVALID, "sbr_create: " + bad); }
+    e->n = n_envs; e->device = device_id; e->first_env_id = first_env_id; e->cfg = c;
     derive_params(c, e->par);
-#define CREATE_TRY(call)                                                                         \
-    do {                                                                                         \
-        hipError_t _s = (call);                                                                  \
-        if (_s != hipSuccess) {                                                                  \
-            std::string m = std::string(#call) + ": " + hipGetErrorString(_s);                   \
-            sbr_destroy(e);                                                                      \
-            return fail(nullptr, _s == hipErrorOutOfMemory ? SBR_ERR_ALLOC : SBR_ERR_HIP, m);    \
-        }                                                                                        \
-    } while (0)
     DeviceGuard guard(device_id);
-    CREATE_TRY(guard.status);
+    HIP_TRY(nullptr, guard.status);
     hipDeviceProp_t prop;
-    CREATE_TRY(hipGetDeviceProperties(&prop, device_id));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
-        std::string m = std::string("sbr_create: device is ") + prop.gcnArchName + ", this build targets gfx950 only";
-        sbr_destroy(e);
-        return fail(nullptr, SBR_ERR_NO_DEVICE, m);
-    }
+    HIP_TRY(nullptr, hipGetDeviceProperties(&prop, device_id));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return fail(nullptr, SBR_ERR_NO_DEVICE, std::string("sbr_create: device is ") + prop.gcnArchName + ", this build targets gfx950 only");
     e->one_wave_envs = (int64_t)prop.multiProcessorCount * 4 * 64;
     const size_t nb = (size_t)n_envs * sizeof(double);
-    CREATE_TRY(hipMalloc(&e->buf.x, SBR_NX * nb));
-    CREATE_TRY(hipMalloc(&e->buf.ctrl, R_NROWS * nb));
-    CREATE_TRY(hipMalloc(&e->buf.infl, SBR_NX * nb));
-    CREATE_TRY(hipMalloc(&e->tables, 2 * kTableDoubles * sizeof(double)));
-    CREATE_TRY(hipMemset(e->buf.x, 0, SBR_NX * nb));
-    CREATE_TRY(hipMemset(e->buf.ctrl, 0, R_NROWS * nb));
-    CREATE_TRY(hipMemset(e->buf.infl, 0, SBR_NX * nb));
+    HIP_TRY(nullptr, hipMalloc(&e->buf.x, SBR_NX * nb));
+    HIP_TRY(nullptr, hipMalloc(&e->buf.ctrl, R_NROWS * nb));
+    HIP_TRY(nullptr, hipMalloc(&e->buf.infl, SBR_NX * nb));
+    HIP_TRY(nullptr, hipMalloc(&e->tables, 2 * kTableDoubles * sizeof(double)));
+    HIP_TRY(nullptr, hipMemset(e->buf.x, 0, SBR_NX * nb));
+    HIP_TRY(nullptr, hipMemset(e->buf.ctrl, 0, R_NROWS * nb));
+    HIP_TRY(nullptr, hipMemset(e->buf.infl, 0, SBR_NX * nb));
     // an env is unusable until its first reset: mark everything done so that step() is a no-op until then; filled on the
     // device, no host staging buffer
     hipLaunchKernelGGL(k_fill, grid_for(n_envs), dim3(SBR_BLOCK), 0, nullptr, e->buf.ctrl + (size_t)R_META * n_envs, n_envs,
                        SbrMeta::pack({0, 0, true}));
-    CREATE_TRY(hipGetLastError());
-    CREATE_TRY(hipDeviceSynchronize());
-    CREATE_TRY(hipEventCreate(&e->ev0));
-    CREATE_TRY(hipEventCreate(&e->ev1));
-    {
-        const int lds_bytes = kLdsTableDoubles * (int)sizeof(double);      // 84 KiB of dynamic LDS: above the 64 KiB default
-        for (const int c : {0, 1}) {
-            const void* fns[6] = {(const void*)kReset<float, SBR_RESET_BLOCK>[c], (const void*)kReset<double, SBR_RESET_BLOCK>[c],
-                                  (const void*)kReset<float, 512>[c], (const void*)kReset<double, 512>[c],
-                                  (const void*)kCycleReset<float>[c], (const void*)kCycleReset<double>[c]};
-            for (const void* fn : fns) CREATE_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        }
+    HIP_TRY(nullptr, hipGetLastError());
+    HIP_TRY(nullptr, hipDeviceSynchronize());
+    HIP_TRY(nullptr, hipEventCreate(&e->ev0));
+    HIP_TRY(nullptr, hipEventCreate(&e->ev1));
+    const int lds_bytes = kLdsTableDoubles * (int)sizeof(double);      // 84 KiB of dynamic LDS: above the 64 KiB default
+    for (const int carry : {0, 1}) {
+        const void* fns[6] = {(const void*)kReset<float, SBR_RESET_BLOCK>[carry], (const void*)kReset<double, SBR_RESET_BLOCK>[carry],
+                              (const void*)kReset<float, 512>[carry], (const void*)kReset<double, 512>[carry],
+                              (const void*)kCycleReset<float>[carry], (const void*)kCycleReset<double>[carry]};
+        for (const void* fn : fns) HIP_TRY(nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     }
-#undef CREATE_TRY
     e->buf.n = n_envs; e->buf.first_env_id = first_env_id;
-    *out = e;
+    *out = e.release();
     return SBR_OK;
 }
 
@@ -1395,34 +1397,37 @@ int sbr_set_influent_tables(sbr_env* e, const double* means, const double* stds)
     return SBR_OK;
 }
 
-static int reset_impl(sbr_env* e, bool carry, uint64_t seed, const int32_t* scenario, const double* rnd,
-                      const double* influent, const uint8_t* mask, void* obs, void* stream) {
+// k_reset and k_cycle_reset take the same arguments and stage the same tables; `who` is the entry point named in the message
+static int reset_impl(sbr_env* e, const char* who, bool cycle, bool carry, uint64_t seed, const int32_t* scenario,
+                      const double* rnd, const double* influent, const uint8_t* mask, void* obs, void* stream) {
     if (!e) return SBR_ERR_INVALID;
     if (!influent && !e->have_tables)
-        return fail(e, SBR_ERR_INVALID, "sbr_reset: no influent given and sbr_set_influent_tables was never called");
-    ON_DEVICE(e);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = influent ? 0 : kLdsTableDoubles * sizeof(double);
-    const int blk = reset_block(e);
-    const dim3 grid((unsigned)((e->n + blk - 1) / blk));
-    if (e->cfg.out_f64)
-        hipLaunchKernelGGL((blk == 512 ? kReset<double, 512> : kReset<double, SBR_RESET_BLOCK>)[carry], grid, dim3(blk), lds, st,
-                           e->par, e->buf, e->tables, seed, scenario, rnd, influent, mask, (double*)obs);
-    else
-        hipLaunchKernelGGL((blk == 512 ? kReset<float, 512> : kReset<float, SBR_RESET_BLOCK>)[carry], grid, dim3(blk), lds, st,
-                           e->par, e->buf, e->tables, seed, scenario, rnd, influent, mask, (float*)obs);
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+        return fail(e, SBR_ERR_INVALID, std::string(who) + ": no influent given and sbr_set_influent_tables was never called");
+    return launched(e, [&] {
+        const size_t lds = influent ? 0 : kLdsTableDoubles * sizeof(double);
+        const int blk = cycle ? SBR_RESET_BLOCK : reset_block(e);
+        dispatch(e, [&](auto c) {
+            using T = typename decltype(c)::OutT;
+            const ResetFn<T> fn = (cycle ? kCycleReset<T> : blk == 512 ? kReset<T, 512> : kReset<T, SBR_RESET_BLOCK>)[carry];
+            hipLaunchKernelGGL(fn, dim3((unsigned)((e->n + blk - 1) / blk)), dim3(blk), lds, (hipStream_t)stream, e->par, e->buf,
+                               e->tables, seed, scenario, rnd, influent, mask, (T*)obs);
+        });
+    });
 }
 
 int sbr_reset(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* rnd, const double* influent,
               const uint8_t* mask, void* obs, void* stream) {
-    return reset_impl(e, false, seed, scenario, rnd, influent, mask, obs, stream);
+    return reset_impl(e, "sbr_reset", false, false, seed, scenario, rnd, influent, mask, obs, stream);
 }
 
 int sbr_reset_carry(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* rnd, const double* influent,
                     const uint8_t* mask, void* obs, void* stream) {
-    return reset_impl(e, true, seed, scenario, rnd, influent, mask, obs, stream);
+    return reset_impl(e, "sbr_reset", false, true, seed, scenario, rnd, influent, mask, obs, stream);
+}
+
+int sbr_cycle_reset(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* rnd, const double* influent,
+                    const uint8_t* mask, int32_t carry_over, void* obs, void* stream) {
+    return reset_impl(e, "sbr_cycle_reset", true, carry_over != 0, seed, scenario, rnd, influent, mask, obs, stream);
 }
 
 int sbr_set_trace(sbr_env* e, double* buf, int64_t n_envs, int64_t capacity, int32_t record_width) {
@@ -1437,74 +1442,61 @@ int sbr_set_trace(sbr_env* e, double* buf, int64_t n_envs, int64_t capacity, int
 
 int sbr_step(sbr_env* e, const void* action, void* obs, void* state, void* reward, uint8_t* done, void* stream) {
     if (!e || !action) return fail(e, SBR_ERR_INVALID, "sbr_step: NULL env or action");
-    ON_DEVICE(e);
-    hipStream_t st = (hipStream_t)stream;
-    if (e->cfg.out_f64) {
-        if (e->cfg.act_f64) launch_step<double, double>(e, action, obs, state, reward, done, st);
-        else launch_step<double, float>(e, action, obs, state, reward, done, st);
-    } else {
-        if (e->cfg.act_f64) launch_step<float, double>(e, action, obs, state, reward, done, st);
-        else launch_step<float, float>(e, action, obs, state, reward, done, st);
-    }
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
-}
-
-int sbr_cycle_reset(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* rnd, const double* influent,
-                    const uint8_t* mask, int32_t carry_over, void* obs, void* stream) {
-    if (!e) return SBR_ERR_INVALID;
-    if (!influent && !e->have_tables)
-        return fail(e, SBR_ERR_INVALID, "sbr_cycle_reset: no influent given and sbr_set_influent_tables was never called");
-    ON_DEVICE(e);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = influent ? 0 : kLdsTableDoubles * sizeof(double);
-    const dim3 grid((unsigned)((e->n + SBR_RESET_BLOCK - 1) / SBR_RESET_BLOCK)), blk(SBR_RESET_BLOCK);
-    if (e->cfg.out_f64)
-        hipLaunchKernelGGL(kCycleReset<double>[carry_over != 0], grid, blk, lds, st, e->par, e->buf, e->tables, seed, scenario, rnd,
-                           influent, mask, (double*)obs);
-    else
-        hipLaunchKernelGGL(kCycleReset<float>[carry_over != 0], grid, blk, lds, st, e->par, e->buf, e->tables, seed, scenario, rnd,
-                           influent, mask, (float*)obs);
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] {
+        const int blk = step_block(e);
+        const uint32_t flags = ((e->par.KcD_DO != 0.0 || e->par.KcD_EC != 0.0 || e->buf.trace != nullptr) ? SBR_KF_NEED_M2 : 0u) |
+                               (blk == 256 ? SBR_KF_STAGGER : 0u);
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            using OutT = typename C::OutT;
+            using ActT = typename C::ActT;
+            // scheme 0 has no two-waves build (step_waves is 1 for it)
+            auto fn = k_step<OutT, ActT, 64, C::OCI, C::SCH>;
+            if (blk == 256)
+                fn = step_waves(e) == 2 ? k_step<OutT, ActT, 256, C::OCI, C::SCH, C::SCH == 1 ? 2 : 1> : k_step<OutT, ActT, 256, C::OCI, C::SCH>;
+            hipLaunchKernelGGL(fn, dim3((unsigned)((e->n + blk - 1) / blk)), dim3(blk), 0, (hipStream_t)stream, e->buf.x, e->buf.ctrl,
+                               e->buf.n, (const ActT*)action, flags, (OutT*)obs, (OutT*)state, (OutT*)reward, done, e->par, e->buf);
+        });
+    });
 }
 
 int sbr_cycle_step(sbr_env* e, const void* action, void* obs, void* reward, double* diag, void* stream) {
     if (!e || !action) return fail(e, SBR_ERR_INVALID, "sbr_cycle_step: NULL env or action");
-    ON_DEVICE(e);
-    hipStream_t st = (hipStream_t)stream;
-    if (e->cfg.out_f64) {
-        if (e->cfg.act_f64) launch_cycle<double, double>(e, action, obs, reward, diag, st);
-        else launch_cycle<double, float>(e, action, obs, reward, diag, st);
-    } else {
-        if (e->cfg.act_f64) launch_cycle<float, double>(e, action, obs, reward, diag, st);
-        else launch_cycle<float, float>(e, action, obs, reward, diag, st);
-    }
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] {
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            using T = typename C::OutT;
+            using A = typename C::ActT;
+            const auto fn = fused_waves(e) == 1 ? k_cycle<T, A, C::SCH, kFusedOneWave<C::SCH>> : k_cycle<T, A, C::SCH, 2>;
+            hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, (const A*)action, (T*)obs,
+                               (T*)reward, diag);
+        });
+    });
 }
 
 int sbr_rollout(sbr_env* e, int32_t n_steps, uint64_t policy_seed, double* returns, float* actions_out, void* stream) {
     if (!e || n_steps < 0) return fail(e, SBR_ERR_INVALID, "sbr_rollout: bad argument");
-    ON_DEVICE(e);
-    if (e->cfg.reward_kind == 2) launch_rollout<true>(e, n_steps, policy_seed, returns, actions_out, (hipStream_t)stream);
-    else launch_rollout<false>(e, n_steps, policy_seed, returns, actions_out, (hipStream_t)stream);
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] {
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            const auto fn = fused_waves(e) == 1 ? k_rollout<C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_rollout<C::OCI, C::SCH, 2>;
+            hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, policy_seed,
+                               returns, actions_out);
+        });
+    });
 }
 
 int sbr_reduce_stats(sbr_env* e, const double* values, int64_t n, double* out4, void* stream) {
     if (!e || !values || !out4 || n < 0) return fail(e, SBR_ERR_INVALID, "sbr_reduce_stats: bad argument");
-    ON_DEVICE(e);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(SBR_BLOCK), 0, st, out4);
-    if (n > 0) {
-        int64_t blocks = (n + SBR_BLOCK - 1) / SBR_BLOCK;
-        if (blocks > 2048) blocks = 2048;      // grid-stride beyond 8 waves per CU
-        hipLaunchKernelGGL(k_stats, dim3((unsigned)blocks), dim3(SBR_BLOCK), 0, st, values, n, out4);
-    }
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] {
+        hipStream_t st = (hipStream_t)stream;
+        hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(SBR_BLOCK), 0, st, out4);
+        if (n > 0) {
+            int64_t blocks = (n + SBR_BLOCK - 1) / SBR_BLOCK;
+            if (blocks > 2048) blocks = 2048;      // grid-stride beyond 8 waves per CU
+            hipLaunchKernelGGL(k_stats, dim3((unsigned)blocks), dim3(SBR_BLOCK), 0, st, values, n, out4);
+        }
+    });
 }
 
 int sbr_get_state(sbr_env* e, double* x, double* ctrl, void* stream) {
@@ -1564,12 +1556,11 @@ int sbr_eval_rhs(sbr_env* e, int32_t kind, int64_t n, const double* x, const dou
                  const double* loading, double* dx, void* stream) {
     if (!e || !x || !kla || !ec || !dx || kind < 0 || kind > 2 || (kind == 1 && !loading))
         return fail(e, SBR_ERR_INVALID, "sbr_eval_rhs: bad argument");
-    ON_DEVICE(e);
-    if (n > 0)
-        hipLaunchKernelGGL(k_rhs, grid_for(n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, kind, n, x, kla, ec,
-                           loading, dx);
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] {
+        if (n > 0)
+            hipLaunchKernelGGL(k_rhs, grid_for(n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, kind, n, x, kla, ec,
+                               loading, dx);
+    });
 }
 
 int sbr_eval_substeps(sbr_env* e, int32_t kind, int64_t n, int32_t n_sub, const double* x0, const double* kla, const double* ec,
@@ -1577,28 +1568,21 @@ int sbr_eval_substeps(sbr_env* e, int32_t kind, int64_t n, int32_t n_sub, const 
     if (!e || !x0 || !kla || !h || !xs || !dxs || n < 0 || n_sub < 1 || n_sub > (1 << 20) || kind < 0 || kind > 3 ||
         (kind == 0 && !ec) || (kind == 1 && !loading))
         return fail(e, SBR_ERR_INVALID, "sbr_eval_substeps: bad argument");
-    ON_DEVICE(e);
-    if (n > 0)
-        hipLaunchKernelGGL(k_substeps, grid_for(n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, kind, n, n_sub, x0, kla, ec,
-                           loading, h, xs, dxs);
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] {
+        if (n > 0)
+            hipLaunchKernelGGL(k_substeps, grid_for(n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, kind, n, n_sub, x0, kla, ec,
+                               loading, h, xs, dxs);
+    });
 }
 
 int sbr_draw_normals(sbr_env* e, uint64_t seed, double* out, void* stream) {
     if (!e || !out) return fail(e, SBR_ERR_INVALID, "sbr_draw_normals: NULL argument");
-    ON_DEVICE(e);
-    hipLaunchKernelGGL(k_normals, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->buf, seed, out);
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] { hipLaunchKernelGGL(k_normals, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->buf, seed, out); });
 }
 
 int sbr_draw_scenarios(sbr_env* e, uint64_t seed, int32_t* out, void* stream) {
     if (!e || !out) return fail(e, SBR_ERR_INVALID, "sbr_draw_scenarios: NULL argument");
-    ON_DEVICE(e);
-    hipLaunchKernelGGL(k_scenarios, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->buf, seed, out);
-    HIP_TRY(e, hipGetLastError());
-    return SBR_OK;
+    return launched(e, [&] { hipLaunchKernelGGL(k_scenarios, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->buf, seed, out); });
 }
 
 #ifdef SBR_STAMPS

@@ -3,7 +3,6 @@
 All numbers come from libsbr_amd.so; there is no CPU path."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import _capi
@@ -22,25 +21,16 @@ class SbrEnv2Vec(SbrOSVec):
         self.all_done = torch.ones((n,), dtype=torch.uint8, device=dev)
 
     def reset(self, seed=0, scenario=None, rnd=None, influent=None, mask=None, carry_over=False):
-        n = self.num_envs
-        sc = self._dev(scenario, torch.int32, (n,))
-        rn = self._dev(rnd, torch.float64, (n, _capi.NSAMP))
-        inf = self._dev(influent, torch.float64, (n, _capi.NX))
-        mk = self._dev(mask, torch.uint8, (n,))
+        ins = self._reset_inputs(scenario, rnd, influent, mask)
         with torch.cuda.device(self.device):
-            _capi.check(self.lib.sbr_cycle_reset(self._h, C.c_uint64(int(seed)), _ptr(sc), _ptr(rn), _ptr(inf), _ptr(mk),
-                                                 1 if carry_over else 0, _ptr(self.cobs), self._stream()), self._h)
-        self._keep = (sc, rn, inf, mk)
+            _capi.check(self.lib.sbr_cycle_reset(self._h, C.c_uint64(int(seed)), *ins, 1 if carry_over else 0, _ptr(self.cobs),
+                                                 self._stream()), self._h)
         return self.cobs
 
     def step(self, action, want_diag=True):
-        a = action if (isinstance(action, torch.Tensor) and action.dtype == self.action_dtype and action.is_contiguous()
-                       and action.device == self.device) else self._dev(action, self.action_dtype, (self.num_envs, 3))
-        if tuple(a.shape) != (self.num_envs, 3):
-            raise ValueError("action must have shape [N,3]")
+        a = self._action(action, (self.num_envs, _capi.NCYC_ACT))
         _capi.check(self.lib.sbr_cycle_step(self._h, _ptr(a), _ptr(self.cobs), _ptr(self.reward),
                                             _ptr(self.diag) if want_diag else None, self._stream()), self._h)
-        self._keep_a = a
         return self.cobs, self.reward, self.all_done
 
     def rollout(self, *a, **k):

@@ -112,6 +112,22 @@ class SbrOSVec:
             raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
         return t
 
+    def _reset_inputs(self, scenario, rnd, influent, mask):
+        """reset()'s optional inputs as device pointers; the tensors stay alive until the stream has consumed them."""
+        n = self.num_envs
+        self._keep = (self._dev(scenario, torch.int32, (n,)), self._dev(rnd, torch.float64, (n, _capi.NSAMP)),
+                      self._dev(influent, torch.float64, (n, _capi.NX)), self._dev(mask, torch.uint8, (n,)))
+        return [_ptr(t) for t in self._keep]
+
+    def _action(self, action, shape):
+        """An action as a contiguous device tensor of the env's action dtype and of `shape` = (N, width), kept alive."""
+        a = action if (isinstance(action, torch.Tensor) and action.dtype == self.action_dtype and action.is_contiguous()
+                       and action.device == self.device) else self._dev(action, self.action_dtype, shape)
+        if a.shape != shape:
+            raise ValueError("action must have shape [N,%d]" % shape[1])
+        self._keep_a = a
+        return a
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             torch.cuda.synchronize(self.device)
@@ -128,16 +144,10 @@ class SbrOSVec:
     def reset(self, seed=0, scenario=None, rnd=None, influent=None, mask=None, carry_over=False):
         """carry_over=True starts the new cycle from each env's own current state (multi-cycle operation: x0 := x,
         IV := x[0]; disabled in the reference, gym_SBR_oneshot.py:260-268) instead of the configured start state."""
-        n = self.num_envs
-        sc = self._dev(scenario, torch.int32, (n,))
-        rn = self._dev(rnd, torch.float64, (n, _capi.NSAMP))
-        inf = self._dev(influent, torch.float64, (n, _capi.NX))
-        mk = self._dev(mask, torch.uint8, (n,))
+        ins = self._reset_inputs(scenario, rnd, influent, mask)
         with torch.cuda.device(self.device):
             fn = self.lib.sbr_reset_carry if carry_over else self.lib.sbr_reset
-            _capi.check(fn(self._h, C.c_uint64(int(seed)), _ptr(sc), _ptr(rn), _ptr(inf), _ptr(mk), _ptr(self.obs),
-                           self._stream()), self._h)
-        self._keep = (sc, rn, inf, mk)      # keep inputs alive until the stream has consumed them
+            _capi.check(fn(self._h, C.c_uint64(int(seed)), *ins, _ptr(self.obs), self._stream()), self._h)
         return self.obs
 
     def step(self, action):
