@@ -12,9 +12,6 @@ from oracle import sbr_oracle as O                     # noqa: E402
 from tests.conftest import EPISODES, golden            # noqa: E402
 
 lib, p = O.lib(), O.default_params()
-lib.sbro_rhs_reaction.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double)]
-lib.sbro_rk4.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_double, C.c_double,
-                         C.POINTER(C.c_double)]
 scale = np.array([1.32, 30, 30, 1500, 150, 3000, 2000, 600, 8, 20, 20, 10, 10, 10.])
 SO = 8
 
@@ -24,9 +21,7 @@ def gate(x, ref):
 
 
 def f(x, kla, ec):
-    d = np.empty(14)
-    lib.sbro_rhs_reaction(C.byref(p), O._p(np.ascontiguousarray(x)), kla, ec, O._p(d))
-    return d
+    return O.rhs_reaction(x, kla, ec, params=p)
 
 
 def so_rate(x, kla, ec):

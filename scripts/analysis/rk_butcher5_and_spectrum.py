@@ -6,7 +6,6 @@ for name in EPISODES:
     e = golden("sbros_" + name)
     for i in range(len(e["iv_kind"])):
         ivs.append((e["iv_x_start"][i], float(e["iv_t_end"][i]) - float(e["iv_t_start"][i]), float(e["iv_Kla"][i]), float(e["iv_EC"][i]), e["iv_x_end"][i]))
-lib.sbro_rk4.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]
 step, stages = B5
 for n in (4, 5):
     w_exact = w_ref = 0; wk = None

@@ -6,9 +6,7 @@ from tests.conftest import EPISODES, golden
 lib = O.lib(); p = O.default_params()
 scale = np.array([1.32,30,30,1500,150,3000,2000,600,8,20,20,10,10,10.])
 def gate(x, ref): return (np.abs(x - ref) / (1e-5*np.abs(ref) + 1e-5*scale)).max()
-lib.sbro_rhs_reaction.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double)]
-def f(x, kla, ec):
-    d = np.empty(14); lib.sbro_rhs_reaction(C.byref(p), O._p(np.ascontiguousarray(x)), kla, ec, O._p(d)); return d
+def f(x, kla, ec): return O.rhs_reaction(x, kla, ec, params=p)
 
 def erk(A, b, c=None):
     A = [np.array(r, dtype=float) for r in A]; b = np.array(b, dtype=float)
@@ -52,7 +50,6 @@ for name in EPISODES:
         ivs.append((e["iv_x_start"][i], float(e["iv_t_end"][i]) - float(e["iv_t_start"][i]), float(e["iv_Kla"][i]), float(e["iv_EC"][i])))
 print(len(ivs), "intervals")
 # exact: RK4 with 80 substeps through the C routine
-lib.sbro_rk4.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]
 exact = []
 for x0, span, kla, ec in ivs:
     x = x0.copy(); lib.sbro_rk4(C.byref(p), 0, O._p(x), span, 160, kla, ec, None); exact.append(x)

@@ -51,7 +51,6 @@ def episode_figures(name, tables, lam_every=4):
     means, stds = tables
     e, t = golden("sbros_" + name), golden("sbros_%s_tight" % name)
     lib, p0 = O.lib(), O.default_params(scheme=0)
-    lib.sbro_rhs_reaction.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double)]
     nv, n = valid_calls(e), int(e["n_calls"])
     scen = int(e["scenario"])
     out = {"scenario": scen, "valid_calls": nv, "domain_exit_call": int(e["domain_exit_call"]) if "domain_exit_call" in e.files else -1}

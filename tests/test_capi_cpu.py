@@ -75,6 +75,25 @@ def test_default_config_is_the_reference():
         elif name != "out_f64":          # the oracle always returns float64
             assert a == b, name
     assert list(cfg.t_ratio) == c["t_ratio"].tolist() and (cfg.cyc_Kc, cfg.cyc_tauI, cfg.cyc_tauD, cfg.cyc_dt) == (5.0, 0.00035, 0.005, 0.02 / 24)
+    # ... and OracleBatch.load_state reads the product's controller block by the binding's row numbers
+    rows = ("C_T C_SO_M1 C_SO_M2 C_SNO_M1 C_SNO_M2 C_IE_DO C_IE_EC C_EC_LAST C_KLA_HIST0 C_KLA_LAST C_QW C_RETURN C_STEPS C_DONE "
+            "C_STATUS C_KLA_SUM").split()
+    assert [getattr(O, r) for r in rows] == [getattr(_capi, r) for r in rows] and O.KLA_HIST == _capi.KLA_HIST
+
+
+def test_every_oracle_function_is_declared_once_and_bound():
+    """The twin of test_every_declared_symbol_is_exported_and_bound for the checker: oracle/sbr_oracle.py declares restype and
+    argtypes of exactly the functions oracle/sbr_oracle.c exports, and each of them resolves in the loaded library."""
+    from oracle import sbr_oracle as O
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "oracle", "sbr_oracle.c")).read(), flags=re.S)
+    defined = re.findall(r"^(static\s+)?[a-z_0-9]+\s+\*?(sbro_[a-z_0-9]+)\s*\([^;{]*\)\s*\{", text, re.M)
+    exported = sorted(name for static, name in defined if not static)
+    assert len(exported) >= 28 and "sbro_scenario_draw" in exported and "sbro_set_plan_knobs" in exported
+    assert exported == sorted(O.ABI), set(exported) ^ set(O.ABI)
+    raw = C.CDLL(O.build())
+    for name, (res, args) in O.ABI.items():
+        fn = getattr(O.lib(), name)
+        assert getattr(raw, name) is not None and (fn.restype, list(fn.argtypes)) == (res, args), name
 
 
 def test_packaged_influent_tables_are_the_captured_ones():

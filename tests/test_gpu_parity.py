@@ -609,11 +609,9 @@ def test_g2anet_reward_option(G, tables):
     env = G.SbrOSVec(n, out_dtype=torch.float64, config=cfg)
     x = k["X"].T.copy(); ctrl = np.zeros((_capi.NCTRL, n)); ctrl[_capi.C_T] = 0.45
     env.set_state(x, ctrl)
-    import ctypes as C
-    fn = O.lib().sbro_reward_g2anet; fn.restype = C.c_double
     _, _, r, _ = env.step(torch.zeros(n, 2))
     x1, _ = env.get_state()
-    want = np.array([fn(O._p(np.ascontiguousarray(v))) for v in _np(x1).T])
+    want = O.reward_g2anet(_np(x1).T)
     finite = np.isfinite(want)
     assert np.array_equal(np.isfinite(_np(r)), finite) and finite.sum() >= 90
     assert np.abs(_np(r)[finite] - want[finite]).max() < 1e-14

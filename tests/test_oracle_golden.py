@@ -375,11 +375,8 @@ def test_control_rounding_noise_is_amplified_to_gate_level_by_the_closed_loop(ta
 def test_g2anet_reward_known_answers():
     """cfg.reward_kind = 1: module_reward_continuous_G2ANET.py, values from the reference function itself on 96 states
     that straddle every kink (Ss = 0, 10; So = 1.5; Sno, Snh = 4)."""
-    import ctypes as C
     k = golden("reward_g2anet_kat")
-    fn = O.lib().sbro_reward_g2anet
-    fn.restype = C.c_double
-    got = np.array([fn(O._p(np.ascontiguousarray(x))) for x in k["X"]])
+    got = O.reward_g2anet(k["X"])
     assert np.array_equal(got, k["reward"])
     assert len(set(np.round(k["reward"], 6))) > 40
 
@@ -387,13 +384,9 @@ def test_g2anet_reward_known_answers():
 def test_oci_reward_known_answers():
     """cfg.reward_kind = 2: module_reward_continuous.py:4-65 (reward of SbrEnv3/SbrEnv4), values from the reference
     function itself on 120 ragged Kla lists: all three batch_type branches, ammonia either side of the 4 g/m3 penalty."""
-    import ctypes as C
     k = golden("reward_oci_kat")
-    fn = O.lib().sbro_reward_oci
-    fn.restype = C.c_double
-    fn.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]
-    got = np.array([fn(k["so_sat"][i], k["kla_last"][i], k["kla_sum"][i], int(k["batch_type"][i]), k["qin"][i],
-                       k["qw"][i], k["q_eff"][i], k["snh_eff"][i]) for i in range(len(k["reward"]))])
+    got = np.array([O.reward_oci(k["so_sat"][i], k["kla_last"][i], k["kla_sum"][i], int(k["batch_type"][i]), k["qin"][i],
+                                 k["qw"][i], k["q_eff"][i], k["snh_eff"][i]) for i in range(len(k["reward"]))])
     assert np.array_equal(got, k["reward"])
     assert set(k["batch_type"].tolist()) == {0, 1, 2} and (k["reward"] < -200).sum() >= 5      # penalty branch taken
 
@@ -433,11 +426,7 @@ def test_substep_count_is_set_by_accuracy_and_stability():
     own LSODA end state: 8 substeps of classical RK4 miss the 1e-5 gate, 10 meet it with a factor ~2 in hand, and the error
     falls as h^4 (so it is truncation error, not the reference's).  Stability: h = dt keeps lambda*h of the stiffest mode seen on
     the golden states near 1, well inside RK4's real stability interval of 2.785."""
-    import ctypes as C
-    lib, p = O.lib(), O.default_params()
-    lib.sbro_rk4.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_double, C.c_double,
-                             C.POINTER(C.c_double)]
-    lib.sbro_rhs_reaction.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double)]
+    p = O.default_params()
     worst = {n: 0.0 for n in (6, 8, 10, 20)}
     count, lam_max = 0, 0.0
     for name in EPISODES:
@@ -446,17 +435,15 @@ def test_substep_count_is_set_by_accuracy_and_stability():
             span = float(e["iv_t_end"][i]) - float(e["iv_t_start"][i])
             kla, ec = float(e["iv_Kla"][i]), float(e["iv_EC"][i])
             for n in worst:
-                x = e["iv_x_start"][i].copy()
-                lib.sbro_rk4(C.byref(p), 0, O._p(x), span, n, kla, ec, None)
+                x = O.rk4(0, e["iv_x_start"][i], span, n, kla, ec, params=p)
                 worst[n] = max(worst[n], gate(x, e["iv_x_end"][i]).max())
             count += 1
             if i % 8 == 0:          # the stiffest direction is dissolved oxygen: d(dSo/dt)/dSo by central differences
                 x = e["iv_x_start"][i].copy()
                 d = 1e-6
-                xp, xm, fp, fm = x.copy(), x.copy(), np.empty(14), np.empty(14)
+                xp, xm = x.copy(), x.copy()
                 xp[8] += d; xm[8] -= d
-                lib.sbro_rhs_reaction(C.byref(p), O._p(xp), kla, ec, O._p(fp))
-                lib.sbro_rhs_reaction(C.byref(p), O._p(xm), kla, ec, O._p(fm))
+                fp, fm = O.rhs_reaction(xp, kla, ec, params=p), O.rhs_reaction(xm, kla, ec, params=p)
                 lam_max = max(lam_max, abs((fp[8] - fm[8]) / (2 * d)))
     assert count == 2796
     assert worst[8] > 1.0 > worst[10] > 0.3              # measured 1.19 and 0.51
@@ -727,7 +714,6 @@ def test_scheme1_under_perturbed_kinetic_constants():
     Scheme 1 must not be worse than scheme 0 there.  The state-dependent stability floor for the Ss / Snh / Sno modes that
     round 6 built and did not adopt (oracle study knob; 0.2 us per k_step call) would halve what is left: asserted too, so
     that the number stays on record."""
-    import ctypes as C
     import importlib.util
     import os
     from conftest import ROOT
@@ -735,14 +721,11 @@ def test_scheme1_under_perturbed_kinetic_constants():
     pp = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(pp)
     span = (0.25 + P.T_DELTA) - 0.25
-    knobs = O.lib().sbro_set_plan_knobs
-    knobs.argtypes = [C.c_double]
 
     def run(guard):
         rs = np.random.RandomState(3)
-        knobs(2.5 if guard else 0.0)
         g1, g0 = [], []
-        try:
+        with O.plan_knobs(2.5 if guard else 0.0):
             for _ in range(1500):
                 x, kla, ec = pp.sample(rs)
                 x[5], x[6] = rs.uniform(1500, 3000), rs.uniform(80, 200)
@@ -757,8 +740,6 @@ def test_scheme1_under_perturbed_kinetic_constants():
                 g1.append(gate(x1, ex).max() if np.isfinite(x1).all() else 1e30)
                 r = O.rk4(0, x, span, 10, kla, ec, params=p0)
                 g0.append(gate(r, ex).max() if np.isfinite(r).all() else 1e30)
-        finally:
-            knobs(0.0)
         return np.array(g1), np.array(g0)
     g1, g0 = run(False)
     assert len(g1) > 1350
