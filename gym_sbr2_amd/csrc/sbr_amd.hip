@@ -7,6 +7,7 @@
 //              sbr_b5a; scheme 0: 10 RK4 substeps; x2 at phase boundaries), reward,
 //              obs/state, and the terminal phases on the last call of an episode
 //   k_rollout  n_steps fused step()s with an on-device Philox policy, plant state stays in VGPRs
+//   k_rollout_tape   the same under the caller's actions: a tape [rows][N][2], each row held for `hold` calls
 //   k_cycle_reset, k_cycle   the per-cycle env SBR-v2: one launch = one whole 12 h cycle (528 control intervals)
 //   k_export, k_import, k_m1_explicit   public <-> internal controller layout; implicit So[-1] / Sno[-1] made explicit
 //   k_stats    wavefront (DPP) reductions of a per-env vector -> {sum,min,max,count}
@@ -849,6 +850,85 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout(SbrPar p, SbrBuf b
     store_record<OCI>(p, b, i0, l, rec);
     if (returns) returns[i] = acc;
 }
+
+// k_rollout under the CALLER's actions (sbr_rollout_actions): the same calls in the same order - sbr_run_intervals,
+// sbr_finish_step with the register history, sbr_terminal once after the loop - so an env fed the actions k_rollout sampled ends
+// with the same bits.  Only the action source differs: row r of the tape [rows][N][2] is in force for calls r*hold .. r*hold +
+// hold - 1 of THIS launch.  A lane reads its pair of a row with one 8- or 16-byte load (the wave's 64 pairs are contiguous), and
+// the row of call s + 1 is fetched BEFORE call s is integrated: the load's latency passes under the call's arithmetic and not in
+// front of every call.  rewards_out [n_steps][N]: one 512-byte segment per wave and call, 0.0 for a call the env skipped.
+// A kernel of its own and not a template parameter of k_rollout: tests/test_isa_cpu.py addresses k_rollout by its mangled name.
+//
+// A lane's pair of a row as one load (global_load_dwordx2 / dwordx4; the tape only has to be aligned like its elements).  The
+// compiler barrier behind it keeps the load where it is written: without it the compiler sank the fetch of the next row to the
+// end of the call, behind the integration it is meant to overlap, and its whole latency came back in front of the next call's
+// first PID.  (A volatile load stays in place too, but the backend waits for it on the spot: s_waitcnt vmcnt(0) behind the load.)
+typedef float __attribute__((ext_vector_type(2), aligned(4), may_alias)) sbr_act2_f32;
+typedef double __attribute__((ext_vector_type(2), aligned(8), may_alias)) sbr_act2_f64;
+template <typename T> struct SbrAct2;
+template <> struct SbrAct2<float> { using type = sbr_act2_f32; };
+template <> struct SbrAct2<double> { using type = sbr_act2_f64; };
+template <typename ActT>
+SBR_DEV void tape_load(const ActT* row /* the workgroup's part of a row */, uint32_t l, ActT& a0, ActT& a1) {
+    const typename SbrAct2<ActT>::type v = *reinterpret_cast<const typename SbrAct2<ActT>::type*>(row + 2 * l);
+    asm volatile("" ::: "memory");
+    a0 = v.x; a1 = v.y;
+}
+template <typename ActT, bool OCI, int SCH, int WAVES>
+__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout_tape(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold,
+                                                           const ActT* __restrict__ actions, double* __restrict__ returns,
+                                                           double* __restrict__ rewards_out) {
+    const uint32_t l = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * SBR_BLOCK, i = i0 + l;
+    if (i >= b.n) return;
+    if (n_steps == 0) {               // no call: the handle is left as it is (also its plan row)
+        if (returns) returns[i] = 0.0;
+        return;
+    }
+    double x[SBR_NX], xa6[SBR_NXD];
+    SbrX6Reg x6;                      // x6 and the ten Kla values stay in registers, the terminal phases run after the loop: see k_rollout
+    SbrRewardParts rp;
+    load_x(b, i0, l, x);
+    SbrRecord rec;
+    load_record<OCI>(p, b, i0, l, x[8], x[9], rec);
+    SbrCtl& c = rec.c;
+    SbrMeta& m = rec.meta;
+    const ActT* row = actions + i0 * 2;            // the workgroup's part of the row in force (wave-uniform)
+    ActT a0, a1;
+    tape_load(row, l, a0, a1);
+    int32_t left = hold;                           // calls the row in force still covers, this one included
+    double acc = 0.0;
+    bool terminal_due = false;
+    for (int32_t s = 0; s < n_steps; ++s) {
+        ActT n0 = a0, n1 = a1;
+        if (--left == 0 && s + 1 < n_steps) {      // the next call starts a row (wave-uniform): issue its load now
+            row += b.n * 2; left = hold;
+            tape_load(row, l, n0, n1);
+        }
+        double r = 0.0;
+        if (!m.done) {
+            double t_obs;
+            bool dn;
+            sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
+            x6.get(xa6);
+            SbrHistReg hs{rec.hist};
+            r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, rec.qw, rec.ksum, rp);
+            acc += r; rec.ret += r; m.status |= c.st_new;
+            m.steps = SbrMeta::next_steps(m.steps);
+            if (dn) { m.done = true; terminal_due = !OCI && p.terminal; }
+        }
+        if (rewards_out) (rewards_out + ((int64_t)s * b.n + i0))[l] = r;
+        a0 = n0; a1 = n1;
+    }
+    if (terminal_due) {
+        SbrHistReg hs{rec.hist};
+        rec.qw = sbr_terminal<SCH>(p, c, hs, x);
+    }
+    m.plan = 0;                       // a rollout reports no plan
+    store_x(b, i0, l, x);
+    store_record<OCI>(p, b, i0, l, rec);
+    if (returns) returns[i] = acc;
+}
 // ------------------------------------------------------------------------------------------- per-cycle env (SBR-v2)
 // SbrEnv2.reset (gym_SBR_env2.py:69-129): influent draw (scenario 0 by default, :104) and the 3-element observation built
 // from the sums of start state and influent.  CARRY keeps each env's current state as the start state (x0_new, :152).
@@ -1482,6 +1562,21 @@ int sbr_rollout(sbr_env* e, int32_t n_steps, uint64_t policy_seed, double* retur
             const auto fn = fused_waves(e) == 1 ? k_rollout<C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_rollout<C::OCI, C::SCH, 2>;
             hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, policy_seed,
                                returns, actions_out);
+        });
+    });
+}
+
+int sbr_rollout_actions(sbr_env* e, int32_t n_steps, int32_t hold, const void* actions, double* returns, double* rewards_out,
+                        void* stream) {
+    if (!e || n_steps < 0 || hold < 1 || (!actions && n_steps > 0))
+        return fail(e, SBR_ERR_INVALID, "sbr_rollout_actions: need n_steps >= 0, hold >= 1 and an action tape");
+    return launched(e, [&] {
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            using A = typename C::ActT;
+            const auto fn = fused_waves(e) == 1 ? k_rollout_tape<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_rollout_tape<A, C::OCI, C::SCH, 2>;
+            hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold,
+                               (const A*)actions, returns, rewards_out);
         });
     });
 }

@@ -105,6 +105,11 @@ class ShardedSbrOS:
     def rollout(self, n_steps, policy_seed=0):
         return self.env.rollout(n_steps, policy_seed)
 
+    def rollout_actions(self, actions, n_steps=None, hold=1, return_rewards=False):
+        """SbrOSVec.rollout_actions for this rank's block: `actions` [R, n_local, 2] is the rank's own slice of the tape
+        (columns start .. stop - 1 of the global one)."""
+        return self.env.rollout_actions(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards)
+
     def gather_buffers(self, dtype=torch.float32):
         """Caller-owned buffers for gather_episode_returns_into(): (float64 row [n_local], send [n_local] dtype, recv [n_global]
         dtype) on this rank's device.  Only equal shards can be gathered without staging (all_gather_into_tensor)."""

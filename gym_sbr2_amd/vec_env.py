@@ -219,6 +219,32 @@ class SbrOSVec:
                                          self._stream()), self._h)
         return (ret, acts) if return_actions else ret
 
+    def rollout_actions(self, actions, n_steps=None, hold=1, return_rewards=False):
+        """Fused step() calls per env under the CALLER's actions, one launch (sbr_rollout_actions): `actions` is a tape
+        [R, N, 2] (converted to the env's action dtype on the device if needed) whose row r is in force for calls r*hold ..
+        r*hold + hold - 1 of this launch; n_steps defaults to R * hold.  Returns the per-env sum of this launch's rewards [N]
+        float64, with return_rewards=True also the reward of every call [n_steps, N] float64 (0 for a call an env skipped
+        because its episode had ended)."""
+        hold = int(hold)
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        if not (hasattr(actions, "shape") and len(actions.shape) == 3 and tuple(actions.shape[1:]) == self._ashape):
+            raise ValueError("actions must have shape [R,N,2]")
+        rows = int(actions.shape[0])
+        n_steps = rows * hold if n_steps is None else int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must be >= 0")
+        if -(-n_steps // hold) > rows:
+            raise ValueError("%d calls with hold=%d need %d rows of actions, got %d" % (n_steps, hold, -(-n_steps // hold), rows))
+        a = actions if (isinstance(actions, torch.Tensor) and actions.dtype == self.action_dtype and actions.is_contiguous()
+                        and actions.device == self.device) else self._dev(actions, self.action_dtype, actions.shape)
+        self._keep_a = a
+        ret = torch.empty((self.num_envs,), dtype=torch.float64, device=self.device)
+        rew = torch.empty((n_steps, self.num_envs), dtype=torch.float64, device=self.device) if return_rewards else None
+        _capi.check(self.lib.sbr_rollout_actions(self._h, n_steps, hold, _ptr(a) if rows else None, _ptr(ret), _ptr(rew),
+                                                 self._stream()), self._h)
+        return (ret, rew) if return_rewards else ret
+
     def enable_trace(self, n_envs=1, capacity=463):
         """Trajectory export: every step() appends one record (_capi.TR_*: t, x(14), Kla, EC, reward, done, the set-points in
         force, the NO3-PID's e/ie/dcv and the four reward diagnostics) for the first n_envs envs at index = calls since

@@ -289,6 +289,22 @@ int sbr_cycle_step(sbr_env* env, const void* action, void* obs, void* reward, do
 int sbr_rollout(sbr_env* env, int32_t n_steps, uint64_t policy_seed, double* returns, float* actions_out,
                 void* stream);
 
+/* fused rollout over an action tape: n_steps fused step() calls per env in ONE kernel under the CALLER's actions
+ * (open-loop evaluation of set-point sequences, replay of logged episodes, schedule sweeps).
+ *   actions     [ceil(n_steps / hold)][N][2] ActT (float32, or float64 with cfg.act_f64 = 1), DEVICE pointer.
+ *               Row r is in force for calls r*hold .. r*hold + hold - 1 OF THIS LAUNCH
+ *               (row index is launch-relative, not the call count since reset). hold >= 1.
+ *   returns     [N] float64 or NULL: sum of the rewards of this launch's calls, added in call order
+ *   rewards_out [n_steps][N] float64 or NULL: the reward of every call; 0.0 for a call the env skipped
+ *               because its episode had ended (before or during the launch)
+ * Semantics otherwise exactly sbr_rollout's: a finished env ignores the remaining rows, the terminal phases
+ * run once for the done call, SBR_C_PLAN reads 0 afterwards, no trace records, nothing allocated
+ * (graph-capturable).  Fed the actions sbr_rollout sampled (actions_out), an env ends with the same bits.
+ * n_steps = 0 leaves the handle as it is and writes returns = 0.  SBR_ERR_INVALID: NULL env, n_steps < 0, hold < 1,
+ * actions NULL with n_steps > 0. */
+int sbr_rollout_actions(sbr_env* env, int32_t n_steps, int32_t hold, const void* actions,
+                        double* returns, double* rewards_out, void* stream);
+
 /* batch statistics of a per-env float64 vector (e.g. episode returns): wavefront reductions
  * + one atomic per wave.  out4 = {sum, min, max, count} float64, DEVICE pointer. */
 int sbr_reduce_stats(sbr_env* env, const double* values, int64_t n, double* out4, void* stream);
