@@ -38,4 +38,7 @@ def __getattr__(name):          # torch is imported only when the env classes ar
     if name == "ShardedSbrOS":
         from .sharding import ShardedSbrOS
         return ShardedSbrOS
+    if name == "MlpPolicy":
+        from .policy import MlpPolicy
+        return MlpPolicy
     raise AttributeError(name)

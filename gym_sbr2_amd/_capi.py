@@ -45,6 +45,14 @@ class SbrConfig(C.Structure):
         ("scheme", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class SbrPolicy(C.Structure):
+    """struct sbr_policy of include/sbr_amd.h (sbr_rollout_policy)."""
+    _fields_ = [("params", C.c_void_p), ("n_hidden", C.c_int32), ("width", C.c_int32), ("activation", C.c_int32),
+                ("squash", C.c_int32), ("n_policies", C.c_int64), ("envs_per_policy", C.c_int64),
+                ("act_scale", C.c_float * 2), ("act_bias", C.c_float * 2), ("noise_std", C.c_float * 2),
+                ("noise_seed", C.c_uint64)]
+
+
 class SbrError(RuntimeError):
     pass
 
@@ -71,6 +79,8 @@ SYMBOLS = {
     "sbr_cycle_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_rollout": (C.c_int, [_VP, _I32, _U64, _VP, _VP, _VP]),
     "sbr_rollout_actions": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "sbr_policy_param_count": (_I64, [_I32, _I32]),
+    "sbr_rollout_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP]),
     "sbr_reduce_stats": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
     "sbr_get_state": (C.c_int, [_VP, _VP, _VP, _VP]),
     "sbr_set_state": (C.c_int, [_VP, _VP, _VP, _VP]),

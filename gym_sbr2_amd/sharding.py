@@ -110,6 +110,14 @@ class ShardedSbrOS:
         (columns start .. stop - 1 of the global one)."""
         return self.env.rollout_actions(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards)
 
+    def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
+                       return_rewards=False):
+        """SbrOSVec.rollout_policy for this rank's block.  `policy` is the WHOLE population on every rank: an env picks its
+        member by its global id, so the result does not depend on the world size (with more than one member the rank's first
+        global id must be a multiple of 256).  `obs` [n_local, 18] is the rank's own slice."""
+        return self.env.rollout_policy(policy, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed,
+                                       return_actions=return_actions, return_rewards=return_rewards)
+
     def gather_buffers(self, dtype=torch.float32):
         """Caller-owned buffers for gather_episode_returns_into(): (float64 row [n_local], send [n_local] dtype, recv [n_global]
         dtype) on this rank's device.  Only equal shards can be gathered without staging (all_gather_into_tensor)."""

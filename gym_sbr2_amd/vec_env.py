@@ -245,6 +245,43 @@ class SbrOSVec:
                                                  self._stream()), self._h)
         return (ret, rew) if return_rewards else ret
 
+    def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
+                       return_rewards=False):
+        """Fused step() calls per env in CLOSED loop under `policy` (an MlpPolicy, or a population from MlpPolicy.stack), one
+        launch (sbr_rollout_policy): every `hold` calls the net maps the env's float32 observation to the two set-points.
+        `obs` [N, 18] float32 is the observation in force and is updated in place for every env that is not done afterwards;
+        obs=None uses self.obs (converted to float32 and back if the handle's outputs are float64).  noise_std (a number or a
+        pair) adds Gaussian exploration noise keyed by noise_seed, the global env id and the env's call count.  Returns the
+        per-env sum of this launch's rewards [N] float64, then - if asked for - the decisions [ceil(n_steps/hold), N, 2]
+        float32 (exactly the values that were integrated; 0 where an env had finished) and the reward of every call
+        [n_steps, N] float64."""
+        n_steps, hold = int(n_steps), int(hold)
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        if n_steps < 0:
+            raise ValueError("n_steps must be >= 0")
+        n = self.num_envs
+        own = obs is None
+        o = self.obs if own else obs
+        if own and o.dtype != torch.float32:
+            o = o.to(torch.float32)
+        if not (isinstance(o, torch.Tensor) and o.dtype == torch.float32 and o.device == self.device and o.is_contiguous()
+                and tuple(o.shape) == (n, _capi.NOBS)):
+            raise ValueError("obs must be a contiguous float32 tensor of shape [N,%d] on %s (it is updated in place)"
+                             % (_capi.NOBS, self.device))
+        pol = policy.c_struct(self.device, noise_std=noise_std, noise_seed=noise_seed)
+        self._keep_p = (policy, pol, o)
+        ret = torch.empty((n,), dtype=torch.float64, device=self.device)
+        acts = torch.empty((-(-n_steps // hold), n, 2), dtype=torch.float32, device=self.device) if return_actions else None
+        rew = torch.empty((n_steps, n), dtype=torch.float64, device=self.device) if return_rewards else None
+        _capi.check(self.lib.sbr_rollout_policy(self._h, n_steps, hold, C.byref(pol), _ptr(o), _ptr(ret), _ptr(acts), _ptr(rew),
+                                                self._stream()), self._h)
+        if own and o is not self.obs:        # a float64 handle: the rows of the envs that are not done come back, the others stay
+            live = self.ctrl_row(_capi.C_DONE) == 0
+            self.obs.copy_(torch.where(live[:, None], o.to(self.obs.dtype), self.obs))
+        out = (ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ())
+        return out if len(out) > 1 else ret
+
     def enable_trace(self, n_envs=1, capacity=463):
         """Trajectory export: every step() appends one record (_capi.TR_*: t, x(14), Kla, EC, reward, done, the set-points in
         force, the NO3-PID's e/ie/dcv and the four reward diagnostics) for the first n_envs envs at index = calls since

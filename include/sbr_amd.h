@@ -305,6 +305,54 @@ int sbr_rollout(sbr_env* env, int32_t n_steps, uint64_t policy_seed, double* ret
 int sbr_rollout_actions(sbr_env* env, int32_t n_steps, int32_t hold, const void* actions,
                         double* returns, double* rewards_out, void* stream);
 
+/* fused rollout in CLOSED loop under the caller's policy: n_steps fused step() calls per env in ONE kernel, the action of a
+ * decision call being a small MLP applied to the env's float32 observation, evaluated on the device next to the plant
+ * (policy evaluation, evolution strategies and populations, collectors).
+ *
+ * The net maps the 18 observation values to 2 outputs through n_hidden hidden layers of `width` units.  One policy's
+ * parameter block holds its layers in order, each as torch.nn.Linear stores it: W [out][in] row-major, then b [out]; `in`
+ * is 18 for the first layer, `out` is 2 for the last, and sbr_policy_param_count() floats in all (38 without a hidden layer).
+ * The width is exactly 32 or 64; a narrower net is zero-padded by the caller, which changes no bit: a padded unit is
+ * act(0) = 0 and fma(0, h, acc) = acc.  Arithmetic: float32; every pre-activation is acc = b[j], then
+ * acc = fmaf(W[j][k], h[k], acc) for k ascending; hidden units pass through tanhf or max(., 0); the two outputs y become
+ * the action mean a = fmaf(act_scale, squash ? tanhf(y) : y, act_bias).  With noise_std != 0 the action is
+ * (float)((double)a_k + noise_std_k * z_k), (z_0, z_1) one Box-Muller pair of Philox4x32-10 keyed by noise_seed, stream 3,
+ * subsequence = GLOBAL env id, counter = the env's calls since reset.  The env clips the action afterwards, as always.
+ *
+ * A population: n_policies blocks back to back; the env with GLOBAL id g runs policy g / envs_per_policy (n_policies = 1:
+ * every env runs the one policy and envs_per_policy is not read). */
+typedef struct sbr_policy {
+    const float* params;        /* DEVICE pointer, n_policies blocks of sbr_policy_param_count() floats */
+    int32_t n_hidden;           /* 0, 1 or 2 hidden layers */
+    int32_t width;              /* hidden width: 32 or 64 (ignored when n_hidden = 0) */
+    int32_t activation;         /* hidden activation: 0 tanh, 1 relu */
+    int32_t squash;             /* 0: a = bias + scale*y   1: a = bias + scale*tanh(y) */
+    int64_t n_policies;         /* >= 1 */
+    int64_t envs_per_policy;    /* env with GLOBAL id g runs policy g / envs_per_policy */
+    float act_scale[2], act_bias[2];
+    float noise_std[2];         /* 0, 0 = deterministic */
+    uint64_t noise_seed;
+} sbr_policy;
+/* floats in one policy's parameter block; -1 for a shape sbr_rollout_policy refuses */
+int64_t sbr_policy_param_count(int32_t n_hidden, int32_t width);
+/*   obs         [N][18] float32, DEVICE pointer, in and out (whatever cfg.out_f64 says).  On entry the observation in force:
+ *               what sbr_reset or sbr_step last returned for each env.  On exit the current observation of every env that
+ *               is not done; a done env's row is left as it was (the post-terminal observation is sbr_step's business).
+ *   hold        a decision is taken on the calls s of THIS launch with s % hold == 0 and held for `hold` calls
+ *   returns     [N] float64 or NULL: sum of the rewards of this launch's calls, added in call order
+ *   actions_out [ceil(n_steps / hold)][N][2] float32 or NULL: row s / hold is the decision of call s - exactly the value
+ *               that is cast to double and integrated; 0 for a decision an env skipped because its episode had ended
+ *   rewards_out [n_steps][N] float64 or NULL, as in sbr_rollout_actions
+ * Semantics otherwise exactly sbr_rollout_actions': a finished env skips its remaining calls, the terminal phases run once
+ * for the done call, SBR_C_PLAN reads 0 afterwards, no trace records, nothing allocated (graph-capturable); fed its own
+ * actions_out as a tape, sbr_rollout_actions leaves the same bits.  n_steps = 0 touches nothing and writes returns = 0.
+ * SBR_ERR_INVALID: NULL env, policy, params or obs; n_steps < 0; hold < 1; n_hidden outside 0..2; width other than 32 or 64
+ * with n_hidden > 0; an unknown activation or squash; n_policies < 1; a negative or non-finite noise_std; with
+ * n_policies > 1: envs_per_policy or the handle's first_env_id not a (positive) multiple of 256, or
+ * first_env_id + N > n_policies * envs_per_policy. */
+int sbr_rollout_policy(sbr_env* env, int32_t n_steps, int32_t hold, const sbr_policy* policy, float* obs, double* returns,
+                       float* actions_out, double* rewards_out, void* stream);
+
 /* batch statistics of a per-env float64 vector (e.g. episode returns): wavefront reductions
  * + one atomic per wave.  out4 = {sum, min, max, count} float64, DEVICE pointer. */
 int sbr_reduce_stats(sbr_env* env, const double* values, int64_t n, double* out4, void* stream);

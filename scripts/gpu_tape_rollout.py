@@ -42,6 +42,7 @@ def leg_a():
     return env.rollout(CALLS, policy_seed=PSEED)
 
 
+env.reset(seed=SEED, scenario=scen)                    # the policy's Philox counter is the env's call count: record from a reset handle
 _, tape = env.rollout(CALLS, policy_seed=PSEED, return_actions=True)       # the actions of (a), as the tape of (b) and (c)
 
 
@@ -81,6 +82,8 @@ out = {
     "what": "one SBROS-v1 episode, %d envs x %d calls, scenarios 4..7, physical policy; device events, %d interleaved runs per leg, medians"
             % (N, CALLS, RUNS),
     "device": torch.cuda.get_device_name(0),
+    "gcn_arch": getattr(torch.cuda.get_device_properties(0), "gcnArchName", None),
+    "compute_units": torch.cuda.get_device_properties(0).multi_processor_count,
     "library_source_hash": B.source_hash(),
     "a_sbr_rollout": res["a"], "b_sbr_rollout_actions_hold1_f32": res["b"], "c_sbr_step": res["c"],
     "b_over_a_time": b / a, "b_over_c_throughput": c / b,
