@@ -9,11 +9,28 @@ float32, the same net evaluated in float64, the action rounded to float32), rais
 SBR_ST_NONFINITE on any env in 463 calls:
   inputs 202 at 512 envs, hold 1, with nets 14 (no hidden layer), 12 (1 x 32, tanh and relu), 13 (2 x 32 tanh), 42 (2 x 32 relu);
   inputs 303 at 512 envs with net 13, hold 8;  inputs 202 with nets 23 / 24 as a population of 2 x 256 envs;
-  inputs 404 at 4096 envs with net 13;  inputs 202 with net 33 (2 x 20, padded).
+  inputs 404 at 4096 envs with net 13;  inputs 202 with net 33 (2 x 20, padded);
+  inputs 202 at 256 envs (the first 256 rows of the 512-env inputs), hold 1, with the 64-wide nets 52 (1 x 64 tanh), 51 (1 x 64
+  relu), 53 (2 x 64, tanh and relu), 50 (48 + 64, tanh and relu), with net 71 rescaled for squash "none" (test_squash_none), and
+  with net 13 under (scheme, reward) = (0, eqi_oci), (1, g2anet), (1, oci), (0, oci).
 (Rejected by the same check, for the record: nets 11 and 15 without a hidden layer, 13 and 41 with relu, 21 / 22 as a
-population, 31 as the 2 x 20 net - between 3 and 173 of the 512 envs reach negative ammonia under them.)
+population, 31 as the 2 x 20 net - between 3 and 173 of the 512 envs reach negative ammonia under them; of the 64-wide nets
+1 x 64 tanh 50, 51, 54 and relu 50, 60; 2 x 64 tanh 51, 52, 56 and relu 50, 52, 56; 48 + 64 tanh 51, 55 - 58 and relu 55, 56;
+net 75 for squash "none".)
 So the tolerance tests assert that no env is flagged and mask nothing.  (The bit-for-bit comparisons need no such condition;
-the 98 624-env case makes none.)"""
+the 98 624-env case and the population of 64-wide nets make none.)
+
+Which test runs which build of k_rollout_policy<H, OCI, SCH, WAVES> (the host picks H from the net, OCI from reward "oci", and
+(SCH, WAVES) = (1, 1) up to 98 304 envs, (1, 2) above, (0, 2) for scheme 0):
+  (32, no, 1, 1)  every test below that is not named here;  its reward "g2anet" branch: test_schemes_and_rewards_...[1-g2anet]
+  (32, no, 1, 2)  test_two_waves_build_above_98304_envs_matches_small_handles
+  (32, no, 0, 2)  test_schemes_and_rewards_against_the_tape_kernel[0-eqi_oci]
+  (32, yes, 1, 1) test_schemes_and_rewards_against_the_tape_kernel[1-oci]
+  (32, yes, 0, 2) test_schemes_and_rewards_against_the_tape_kernel[0-oci]
+  (64, no, 1, 1)  test_the_64_wide_net_with_real_weights, test_population_of_64_wide_nets, test_padding_changes_no_bit
+  (64, no, 1, 2)  test_two_waves_build_above_98304_envs_matches_small_handles (its second half)
+  (32, yes, 1, 2), (64, no, 0, 2) and the three (64, yes, ...) builds are not run by any test.
+pl.squash == 0: test_squash_none; every other test squashes with tanh."""
 import os
 
 import numpy as np
@@ -88,7 +105,7 @@ def _bound(pol, o, member=0):
     evaluation with fmaf chains (k ascending) and <= 5 ulp tanhf may differ from them, the input itself being off by up to
     2 u |o| (k_step's and the fused kernel's float32 observations may round differently).  u = 2^-24.
       per layer: e_pre = (in + 1) u (|W| |h| + |b|) + |W| e;   e_h = e_pre + 5 u |h_out|   (both activations are 1-Lipschitz)
-      finally:   |d a| <= scale (e_pre + 5 u) + u |a|."""
+      finally:   |d a| <= scale (e_pre + 5 u) + u |a|;   with squash "none":  a = pre,  |d a| <= e_pre + u |a|."""
     blk = pol.block[member].astype(np.float64)
     h = np.asarray(o, dtype=np.float64)
     e = 2 * U * np.abs(h)
@@ -105,6 +122,8 @@ def _bound(pol, o, member=0):
             e = e_pre + 5 * U * np.abs(h)
         fan_in = out
     scale, bias = pol.act_scale.astype(np.float64), pol.act_bias.astype(np.float64)
+    if pol.squash == "none":          # scale 1, bias 0: the kernel's fmaf(1, y, 0) is exact, a = pre and |d a| <= e_pre + u |a|
+        return pre, e_pre + U * np.abs(pre)
     a = bias + scale * np.tanh(pre)
     return a, scale * (e_pre + 5 * U) + U * np.abs(a)
 
@@ -192,6 +211,159 @@ def test_the_plant_integrates_the_actions_it_reports(G, widths, activation, seed
         worst, _ = _lockstep(G, n, inputs, pol, acts, obs0)
         print("%s %s: worst |d a| / bound %.4f" % (widths, activation, worst))
         assert worst <= 1.0
+
+
+def _bits_then_lockstep(G, n, inputs, pol):
+    """The body of test_the_plant_integrates_the_actions_it_reports for any net: handle A in closed loop, handle B on A's
+    reported actions as a tape (bit for bit), then `_lockstep`.  Returns (acts, obs0, worst |d a| / bound)."""
+    from gym_sbr2_amd import _capi
+    a_env, b_env = _env(G, n, inputs), _env(G, n, inputs)
+    obs0 = a_env.obs.clone()
+    ret_a, acts, rew_a = a_env.rollout_policy(pol, STEPS, return_actions=True, return_rewards=True)
+    assert acts.shape == (STEPS, n, 2) and acts.dtype == torch.float32 and rew_a.shape == (STEPS, n)
+    ret_b, rew_b = b_env.rollout_actions(acts, return_rewards=True)
+    _same_state(a_env, b_env)
+    assert torch.equal(ret_a, ret_b) and torch.equal(rew_a, rew_b)
+    _, c = a_env.get_state()
+    assert bool((c[_capi.C_DONE] == 1).all()) and bool((c[_capi.C_STEPS] == STEPS).all()) and bool((c[_capi.C_PLAN] == 0).all())
+    _no_flags(a_env)
+    a_env.close(); b_env.close()
+    worst, _ = _lockstep(G, n, inputs, pol, acts, obs0)
+    return acts, obs0, worst
+
+
+@pytest.mark.parametrize("widths,activation,seed", [((64,), "tanh", 52), ((64,), "relu", 51), ((64, 64), "tanh", 53),
+                                                    ((64, 64), "relu", 53), ((48, 64), "tanh", 50), ((48, 64), "relu", 50)])
+def test_the_64_wide_net_with_real_weights(G, widths, activation, seed):
+    """The H = 64 build (scheme 1, one wave) under nets whose hidden units 32 .. 63 carry weight: every output group j0 = 0 .. 56 of
+    sbr_mlp_layer<18,64,8> and <64,64,8>, their bias addresses and the advance of the block pointer between the layers decide
+    bits here.  256 envs (one workgroup), a whole episode: bits against the tape kernel, then each of the 463 x 256 x 2 reported
+    actions inside its bound against the float64 net on sbr_step's observations.
+    Measured on the MI355X, worst |d a| / bound: (64,) tanh 0.0197, relu 0.0138; (64, 64) tanh 0.0026, relu 0.0020; (48, 64)
+    tanh 0.0027, relu 0.0039.
+    What the check can see.  Zeroing the bias (-0.112) of unit 40 of layer 2 in the checker's copy of the (64, 64) tanh block
+    moves the float64 mean of call 0 by up to 20.2 bounds, and by more than one bound on every env (asserted below).  One
+    float of layer 2 at a unit >= 32 changed in the block the lockstep check reads, on a scratch copy of this case: on the
+    MI355X W2[40][33] + 0.001 gives worst = 0.41, W2[63][5] + 0.001 gives 0.59, W2[32][63] + 0.0001 gives 0.02 - the bound is
+    a worst-case sum and such a change stays inside it; the ratio grows in proportion, so the case fails from about +0.0025 on.
+    The errors it is there for, a float read from a wrong address, are larger: with the same actions taken from the oracle in
+    closed loop (the CPU stand-in of this check) W2[40][33] + 0.01 gives 4.1, + 0.1 gives 40, W2[40][33] := W2[40][34] 104,
+    W2[63][5] := W2[62][5] 39, b2[40] := b2[41] 226, and the case fails."""
+    n = 256
+    inputs = _inputs(n, 202)
+    with pytest.warns(RuntimeWarning, match="64-wide"):
+        pol = _policy(seed, widths, activation)
+    assert pol.width == 64 and pol.n_hidden == len(widths)
+    acts, obs0, worst = _bits_then_lockstep(G, n, inputs, pol)
+    assert float(acts[..., 0].std()) > 1e-3 and float(acts[..., 1].std()) > 1e-3       # a policy, not a constant
+    print("%s %s: worst |d a| / bound %.4f, action std %.3f and %.3f" % (widths, activation, worst, float(acts[..., 0].std()),
+                                                                         float(acts[..., 1].std())))
+    assert worst <= 1.0
+    if widths == (64, 64):
+        l2 = 18 * 64 + 64                                                              # where layer 2 starts in the block
+        w2 = pol.block[0, l2:l2 + 64 * 64].reshape(64, 64)
+        assert np.any(w2[32:] != 0) and np.any(w2[:, 32:] != 0)                        # a full layer, not a padded one
+        if activation == "tanh":
+            # the check has teeth: without the bias of hidden unit 40 of layer 2 the float64 mean leaves the bound
+            unit = 40
+            cut = pol.widened(64)
+            cut.block = pol.block.copy()
+            assert cut.block[0, l2 + 64 * 64 + unit] != 0
+            cut.block[0, l2 + 64 * 64 + unit] = 0.0
+            o = _np(obs0)
+            mean, bound = _bound(pol, o)
+            moved = np.abs(_bound(cut, o)[0] - mean) / bound
+            print("bias of unit %d of layer 2 zeroed: |d mean| / bound up to %.1f" % (unit, moved.max()))
+            assert (moved.max(axis=1) > 1.0).any()
+
+
+def test_squash_none(G):
+    """pl.squash == 0 on the device: the two outputs of the net ARE the set-points (scale 1, bias 0).  Net 71 (2 x 32 tanh) with
+    the last layer scaled by (0.4, 2.0) and shifted by (1.25, 7.5), so that they are set-points: with it the oracle in closed
+    loop (module docstring) flags no env at 256 envs, inputs 202, and the actions span 0.95 .. 1.42 and 6.1 .. 7.1 (seeds 70,
+    72 - 74 and 76 - 79 pass as well, 75 does not).  Bits against the tape kernel, then the lockstep check with `_bound`'s
+    squash-free last step.  Measured on the MI355X: worst |d a| / bound = 0.0424; actions 0.951 .. 1.420 and 6.124 .. 7.073."""
+    from gym_sbr2_amd import MlpPolicy
+    n = 256
+    inputs = _inputs(n, 202)
+    layers = _net(71, (32, 32))
+    w, b = layers[-1]
+    layers[-1] = (w * np.array([0.4, 2.0])[:, None], np.array([1.25, 7.5]) + b)
+    pol = MlpPolicy(layers, squash="none")
+    assert pol.squash == "none" and pol.width == 32
+    assert np.array_equal(pol.act_scale, np.ones(2, np.float32)) and np.array_equal(pol.act_bias, np.zeros(2, np.float32))
+    acts, _, worst = _bits_then_lockstep(G, n, inputs, pol)
+    a = _np(acts)
+    print("squash none: actions %.3f .. %.3f and %.3f .. %.3f, worst |d a| / bound %.4f"
+          % (a[..., 0].min(), a[..., 0].max(), a[..., 1].min(), a[..., 1].max(), worst))
+    assert 0.9 < a[..., 0].min() and a[..., 0].max() < 1.5 and 6.0 < a[..., 1].min() and a[..., 1].max() < 7.2     # unsquashed, unclipped
+    assert float(acts[..., 0].std()) > 1e-3 and float(acts[..., 1].std()) > 1e-3
+    assert worst <= 1.0
+
+
+CONFIGS = [(0, "eqi_oci"), (1, "g2anet"), (1, "oci"), (0, "oci")]
+
+
+@pytest.mark.parametrize("scheme,reward", CONFIGS)
+def test_schemes_and_rewards_against_the_tape_kernel(G, scheme, reward):
+    """The policy builds behind a non-default config - scheme 0 (RK4 x substeps, always the two-waves build), the G2ANET reward (a
+    run-time branch of the non-OCI builds) and the operating-cost reward (the OCI builds: their own record load / store, the
+    running sum(Kla) row, the terminal phases and the end-of-cycle reward inside the done call) - against the tape kernel of
+    the same config on the reported actions: plant, every controller row (C_KLA_SUM and C_QW included), returns and per-call
+    rewards bit for bit.  Net 13 (2 x 32 tanh), 256 envs, inputs 202: the oracle in closed loop flags no env under any of the
+    four configs, and under "oci" it penalises 134 of the 256 envs on the done call.  Measured on the MI355X: 134 of 256
+    done-call rewards below -200 under both schemes (-245.52 .. 0.4811)."""
+    from gym_sbr2_amd import _capi
+    n = 256
+    inputs = _inputs(n, 202)
+    pol = _policy(13, (32, 32))
+
+    def handle():
+        cfg = _capi.default_config(); cfg.scheme = scheme
+        env = _env(G, n, inputs, config=cfg, reward=reward)
+        assert env.cfg.scheme == scheme and env.cfg.reward_kind == _capi.REWARD_KINDS[reward]
+        return env
+
+    a_env, b_env = handle(), handle()
+    assert a_env.query(_capi.Q_ROLLOUT_WAVES) == (2 if scheme == 0 else 1)
+    ret_a, acts, rew_a = a_env.rollout_policy(pol, STEPS, return_actions=True, return_rewards=True)
+    ret_b, rew_b = b_env.rollout_actions(acts, return_rewards=True)
+    _same_state(a_env, b_env)
+    assert torch.equal(ret_a, ret_b) and torch.equal(rew_a, rew_b)
+    _, c = a_env.get_state()
+    assert bool((c[_capi.C_DONE] == 1).all()) and bool((c[_capi.C_STEPS] == STEPS).all()) and bool((c[_capi.C_PLAN] == 0).all())
+    assert torch.equal(c[_capi.C_RETURN], ret_a) and bool(torch.isfinite(ret_a).all())
+    _no_flags(a_env); _no_flags(b_env)
+    assert float(acts[..., 0].std()) > 1e-3 and float(acts[..., 1].std()) > 1e-3
+    last = _np(rew_a[STEPS - 1])
+    print("scheme %d, %s: done-call reward %.4f .. %.4f, %d of %d below -200" % (scheme, reward, last.min(), last.max(),
+                                                                                 (last < -200).sum(), n))
+    if reward == "oci":                   # the ammonia penalty of the end-of-cycle reward: both sides occur
+        assert (last < -200).any() and (last > -200).any()
+    a_env.close(); b_env.close()
+
+
+def test_population_of_64_wide_nets(G):
+    """Two full 2 x 64 nets as a population of 2 x 256 envs, hold 8: the second wave's block starts `stride` = 5 506 floats into
+    the parameters.  Each half equals the single-policy run of a 256-env handle with those global ids, bit for bit."""
+    from gym_sbr2_amd import MlpPolicy
+    n, hold = 512, 8
+    inputs = _inputs(n, 202)
+    with pytest.warns(RuntimeWarning, match="64-wide"):
+        p0, p1 = _policy(53, (64, 64)), _policy(57, (64, 64))
+    pop = MlpPolicy.stack([p0, p1], envs_per_policy=256)
+    assert pop.width == 64 and pop.block.shape == (2, 5506)
+    big = _env(G, n, inputs)
+    ret, acts = big.rollout_policy(pop, STEPS, hold=hold, return_actions=True)
+    assert acts.shape == (58, n, 2)
+    for first, member in ((0, p0), (256, p1)):
+        part = _env(G, 256, inputs, first=first)
+        r, a = part.rollout_policy(member, STEPS, hold=hold, return_actions=True)
+        _same_state(big, part, cols=slice(first, first + 256))
+        assert torch.equal(r, ret[first:first + 256]) and torch.equal(a, acts[:, first:first + 256])
+        part.close()
+    assert not torch.equal(acts[:, :256], acts[:, 256:])
+    big.close()
 
 
 def test_the_reported_actions_are_the_nets(ref):
@@ -319,6 +491,23 @@ def test_two_waves_build_above_98304_envs_matches_small_handles(G):
         rs, as_ = small.rollout_policy(pol, STEPS, hold=hold, return_actions=True)
         xs, cs = small.get_state()
         assert torch.equal(rs, ret[first:first + 64]) and torch.equal(as_, acts[:, first:first + 64])
+        assert torch.equal(xs, x[:, first:first + 64]) and torch.equal(cs, c[:, first:first + 64])
+        small.close()
+    # ... and the H = 64 two-waves build, on the same handle after a reset: the full 2 x 64 tanh net of seed 53, 58 decisions
+    with pytest.warns(RuntimeWarning, match="64-wide"):
+        wide = _policy(53, (64, 64))
+    assert wide.width == 64
+    env.reset(scenario=inputs[0], rnd=inputs[1])
+    ret_w, acts_w = env.rollout_policy(wide, STEPS, hold=hold, return_actions=True)
+    x, c = env.get_state()
+    assert bool((c[_capi.C_DONE] == 1).all()) and bool((c[_capi.C_STEPS] == STEPS).all())
+    assert not torch.equal(acts_w, acts)
+    for first in (0, n // 2 + 37, n - 64):
+        small = _env(G, 64, inputs, first=first)
+        assert small.query(_capi.Q_ROLLOUT_WAVES) == 1
+        rs, as_ = small.rollout_policy(wide, STEPS, hold=hold, return_actions=True)
+        xs, cs = small.get_state()
+        assert torch.equal(rs, ret_w[first:first + 64]) and torch.equal(as_, acts_w[:, first:first + 64])
         assert torch.equal(xs, x[:, first:first + 64]) and torch.equal(cs, c[:, first:first + 64])
         small.close()
     env.close()
