@@ -9,6 +9,8 @@
 //   k_rollout  n_steps fused step()s with an on-device Philox policy, plant state stays in VGPRs
 //   k_rollout_tape   the same under the caller's actions: a tape [rows][N][2], each row held for `hold` calls
 //   k_rollout_policy the same in closed loop: the caller's MLP maps the env's observation to the action, in the lane of the plant
+//   k_lookahead_tape, k_branch_best   the tape kernel as a read-only fan-out: K tapes per env from its current state, nothing of
+//              the handle written; then the per-env winner of the K returns, one wavefront per env
 //   k_cycle_reset, k_cycle   the per-cycle env SBR-v2: one launch = one whole 12 h cycle (528 control intervals)
 //   k_export, k_import, k_m1_explicit   public <-> internal controller layout; implicit So[-1] / Sno[-1] made explicit
 //   k_stats    wavefront (DPP) reductions of a per-env vector -> {sum,min,max,count}
@@ -931,6 +933,105 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout_tape(SbrPar p, Sbr
     if (returns) returns[i] = acc;
 }
 
+// k_rollout_tape as a READ-ONLY fan-out (sbr_lookahead_actions): `fanout` tapes per env, each played from the env's CURRENT plant
+// and controller record, and nothing of the handle written.  One lane per BRANCH j = env * fanout + candidate; the loop body is
+// the tape kernel's - sbr_run_intervals, sbr_finish_step with the register history, a done branch skips - so branch j returns
+// the bits k_rollout_tape returns for an env holding a copy of that state and fed column j of the tape.
+// What is NOT here, and why that changes no returned bit:
+//  * store_x / store_record: the branch's end state is discarded;
+//  * sbr_terminal: settle, draw and idle after the done call move only x and Qw, which nothing reads afterwards (a finished branch
+//    skips every later call); the end-of-cycle reward of the OCI builds is formed inside sbr_finish_step and stays;
+//  * the return row, the call count, the status bits and the plan: they only feed the record's stores.
+// Addressing.  fanout neighbouring lanes read the SAME env, a workgroup spans at most 256 / fanout + 2 envs.  The env of a lane is
+// formed once, as (e0, el): e0 = env of the workgroup's first branch (wave-uniform), el = the lane's env minus e0 (< 258, 32
+// bits).  load_x / load_record take that pair where the other kernels pass (i0, l): every row stays a scalar base plus one
+// 32-bit lane offset, and lanes of one env coalesce into one fetch of its 8 bytes.  The tape and the outputs
+// are B = N * fanout wide and addressed by (j0, l) like the tape kernel's.
+template <typename ActT, bool OCI, int SCH, int WAVES>
+__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_tape(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
+                                                             uint32_t n_branch, const ActT* __restrict__ actions,
+                                                             double* __restrict__ returns, double* __restrict__ rewards_out) {
+    const uint32_t l = threadIdx.x;
+    const uint32_t j0u = blockIdx.x * (uint32_t)SBR_BLOCK;   // n_branch < 2^31 (checked by the host): 32 bits hold every branch index
+    if (j0u + l >= n_branch) return;
+    const int64_t j0 = (int64_t)j0u;
+    if (n_steps == 0) {               // no call: nothing of the state is loaded
+        if (returns) (returns + j0)[l] = 0.0;
+        return;
+    }
+    const uint32_t e0u = j0u / fanout;                       // wave-uniform: one scalar division per launch
+    // el <= l / fanout + 1 <= 256.  The mask changes no value; it tells the backend that el * 8 fits 32 bits, which is what lets
+    // a row access be `global_load v, v_off, s[base]` - without it every row's address was formed per lane in 64 bits
+    const uint32_t el = ((j0u + l) / fanout - e0u) & 511u;
+    const int64_t e0 = (int64_t)e0u;
+    double x[SBR_NX], xa6[SBR_NXD];
+    SbrX6Reg x6;                      // x6 and the ten Kla values stay in registers: see k_rollout
+    SbrRewardParts rp;
+    load_x(b, e0, el, x);
+    SbrRecord rec;
+    load_record<OCI>(p, b, e0, el, x[8], x[9], rec);
+    SbrCtl& c = rec.c;
+    bool done = rec.meta.done;
+    const ActT* row = actions + j0 * 2;            // the workgroup's part of the row in force (wave-uniform)
+    ActT a0, a1;
+    tape_load(row, l, a0, a1);
+    int32_t left = hold;                           // calls the row in force still covers, this one included
+    double acc = 0.0;
+    for (int32_t s = 0; s < n_steps; ++s) {
+        ActT n0 = a0, n1 = a1;
+        if (--left == 0 && s + 1 < n_steps) {      // the next call starts a row (wave-uniform): issue its load now
+            row += (int64_t)n_branch * 2; left = hold;
+            tape_load(row, l, n0, n1);
+        }
+        double r = 0.0;
+        if (!done) {
+            double t_obs;
+            bool dn;
+            sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
+            x6.get(xa6);
+            SbrHistReg hs{rec.hist};
+            r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, rec.qw, rec.ksum, rp);
+            acc += r;
+            if (dn) done = true;
+        }
+        if (rewards_out) (rewards_out + ((int64_t)s * n_branch + j0))[l] = r;
+        a0 = n0; a1 = n1;
+    }
+    if (returns) (returns + j0)[l] = acc;
+}
+
+// The winner of each env's `fanout` branch returns (sbr_lookahead_actions, launched behind k_lookahead_tape on the same stream):
+// one wavefront per env.  Rule (include/sbr_amd.h): the largest return wins, a NaN return compares as -inf, ties go to the lowest
+// candidate; best_return is the winner's return as it stands in `returns` (NaN only if all are NaN or -inf ties with one at a
+// lower index).  Lanes stride over the candidates, then a 64-lane xor butterfly under the same rule, then lane 0 stores: one path
+// for every fanout.
+struct SbrBest {
+    double key, val;      // key: the return with NaN replaced by -inf; val: the return itself
+    uint32_t k;
+    SBR_DEV void take(double key2, double val2, uint32_t k2) {
+        if (key2 > key || (key2 == key && k2 < k)) { key = key2; val = val2; k = k2; }
+    }
+};
+__global__ __launch_bounds__(SBR_BLOCK) void k_branch_best(const double* __restrict__ returns, int64_t n, uint32_t fanout,
+                                                          int32_t* __restrict__ best_index, double* __restrict__ best_return) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t i = (int64_t)blockIdx.x * (SBR_BLOCK / 64) + (threadIdx.x >> 6);     // wave-uniform
+    if (i >= n) return;
+    const double* mine = returns + i * (int64_t)fanout;
+    SbrBest bst{-INFINITY, NAN, 0xffffffffu};      // a lane without a candidate loses every comparison (lane 0 always has k = 0)
+    for (uint32_t k = lane; k < fanout; k += 64u) {
+        const double v = mine[k];
+        bst.take(v != v ? -INFINITY : v, v, k);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        bst.take(__shfl_xor(bst.key, off, 64), __shfl_xor(bst.val, off, 64), (uint32_t)__shfl_xor((int)bst.k, off, 64));
+    if (lane == 0) {
+        if (best_index) best_index[i] = (int32_t)bst.k;
+        if (best_return) best_return[i] = bst.val;
+    }
+}
+
 // k_rollout_tape in CLOSED loop (sbr_rollout_policy): the action of a decision call is the caller's MLP applied to the env's
 // observation, evaluated in the lane that holds the plant.  The loop body is the tape kernel's - sbr_run_intervals,
 // sbr_finish_step with the register history, sbr_terminal once after the loop - so an env fed this kernel's own actions_out as a
@@ -1459,6 +1560,8 @@ static int step_waves(const sbr_env* e) { return e->cfg.scheme == 1 && e->n > st
 // up to 1.5 waves per SIMD (MI355X: 98304 envs) the fused scheme-1 kernels (k_rollout, k_cycle) run their uncapped-register build
 static int64_t fused_one_wave_max(const sbr_env* e) { return e->one_wave_envs + e->one_wave_envs / 2; }
 static int fused_waves(const sbr_env* e) { return e->cfg.scheme == 1 && e->n <= fused_one_wave_max(e) ? 1 : 2; }
+// the same decision for a launch of `lanes` lanes that are not the handle's envs (sbr_lookahead_actions: one lane per branch)
+static int fused_waves_for(const sbr_env* e, int64_t lanes) { return e->cfg.scheme == 1 && lanes <= fused_one_wave_max(e) ? 1 : 2; }
 // more waves than SIMDs: k_reset in 512-thread workgroups, two waves per SIMD
 static int reset_block(const sbr_env* e) { return e->n > e->one_wave_envs ? 512 : SBR_RESET_BLOCK; }
 // the reset kernels of output type T, indexed by CARRY: k_reset in workgroups of BLK threads, k_cycle_reset (same arguments)
@@ -1767,6 +1870,34 @@ int sbr_rollout_actions(sbr_env* e, int32_t n_steps, int32_t hold, const void* a
             hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold,
                                (const A*)actions, returns, rewards_out);
         });
+    });
+}
+
+int sbr_lookahead_actions(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions, double* returns,
+                          double* rewards_out, int32_t* best_index, double* best_return, void* stream) {
+    // every check is evaluated, the LAST failing one is reported - all of them before anything is touched
+    std::string bad;
+    if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
+    if (!actions && n_steps > 0) bad = "NULL actions with n_steps > 0";
+    if (fanout < 1) bad = "fanout must be >= 1";
+    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+    if (hold < 1) bad = "hold must be >= 1";
+    if (n_steps < 0) bad = "n_steps must be >= 0";
+    if (!e) bad = "NULL env";
+    if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_lookahead_actions: " + bad);
+    const int64_t nb = e->n * (int64_t)fanout;
+    return launched(e, [&] {
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            using A = typename C::ActT;
+            // the register budget goes by the lanes of THIS launch, the branches, not by the handle's envs
+            const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_tape<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_tape<A, C::OCI, C::SCH, 2>;
+            hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
+                               (uint32_t)nb, (const A*)actions, returns, rewards_out);
+        });
+        if (best_index || best_return)
+            hipLaunchKernelGGL(k_branch_best, dim3((unsigned)((e->n + SBR_BLOCK / 64 - 1) / (SBR_BLOCK / 64))), dim3(SBR_BLOCK), 0,
+                               (hipStream_t)stream, returns, e->n, (uint32_t)fanout, best_index, best_return);
     });
 }
 

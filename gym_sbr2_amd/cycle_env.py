@@ -35,3 +35,6 @@ class SbrEnv2Vec(SbrOSVec):
 
     def rollout(self, *a, **k):
         raise NotImplementedError("the fused random-policy rollout belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
+    def lookahead(self, *a, **k):
+        raise NotImplementedError("the read-only lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")

@@ -110,6 +110,11 @@ class ShardedSbrOS:
         (columns start .. stop - 1 of the global one)."""
         return self.env.rollout_actions(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards)
 
+    def lookahead(self, actions, n_steps=None, hold=1, return_rewards=False, return_best=False):
+        """SbrOSVec.lookahead for this rank's block: `actions` [R, n_local, K, 2] is the rank's own slice of the candidates
+        (columns start .. stop - 1 of the global ones)."""
+        return self.env.lookahead(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards, return_best=return_best)
+
     def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
                        return_rewards=False):
         """SbrOSVec.rollout_policy for this rank's block.  `policy` is the WHOLE population on every rank: an env picks its

@@ -245,6 +245,38 @@ class SbrOSVec:
                                                  self._stream()), self._h)
         return (ret, rew) if return_rewards else ret
 
+    def lookahead(self, actions, n_steps=None, hold=1, return_rewards=False, return_best=False):
+        """Read-only lookahead, one launch (sbr_lookahead_actions): `actions` is [R, N, K, 2], K candidate tapes per env (converted
+        to the env's action dtype on the device if needed), each played from the env's CURRENT state with the rows held as in
+        rollout_actions; n_steps defaults to R * hold.  The handle is left bit for bit as it was.  Returns the sum of this
+        launch's rewards per candidate [N, K] float64; with return_rewards=True also the reward of every call [n_steps, N, K]
+        float64 (0 for a call a candidate skipped because its episode had ended); with return_best=True also best_index [N]
+        int32 and best_return [N] float64: per env the largest return, NaN counting as -inf, ties to the lowest index."""
+        hold = int(hold)
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        if not (hasattr(actions, "shape") and len(actions.shape) == 4 and int(actions.shape[1]) == self.num_envs
+                and int(actions.shape[2]) >= 1 and int(actions.shape[3]) == 2):
+            raise ValueError("actions must have shape [R,N,K,2] with K >= 1")
+        rows, fanout = int(actions.shape[0]), int(actions.shape[2])
+        n_steps = rows * hold if n_steps is None else int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must be >= 0")
+        if -(-n_steps // hold) > rows:
+            raise ValueError("%d calls with hold=%d need %d rows of actions, got %d" % (n_steps, hold, -(-n_steps // hold), rows))
+        a = actions if (isinstance(actions, torch.Tensor) and actions.dtype == self.action_dtype and actions.is_contiguous()
+                        and actions.device == self.device) else self._dev(actions, self.action_dtype, actions.shape)
+        self._keep_a = a
+        n, dev = self.num_envs, self.device
+        ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
+        rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
+        bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
+        br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
+        _capi.check(self.lib.sbr_lookahead_actions(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, _ptr(ret), _ptr(rew),
+                                                   _ptr(bi), _ptr(br), self._stream()), self._h)
+        out = (ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ())
+        return out if len(out) > 1 else ret
+
     def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
                        return_rewards=False):
         """Fused step() calls per env in CLOSED loop under `policy` (an MlpPolicy, or a population from MlpPolicy.stack), one

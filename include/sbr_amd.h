@@ -305,6 +305,30 @@ int sbr_rollout(sbr_env* env, int32_t n_steps, uint64_t policy_seed, double* ret
 int sbr_rollout_actions(sbr_env* env, int32_t n_steps, int32_t hold, const void* actions,
                         double* returns, double* rewards_out, void* stream);
 
+/* read-only lookahead: `fanout` action tapes per env, each played from the env's CURRENT state, the handle left bit for bit as
+ * it was (receding-horizon planning: score K candidate set-point sequences per live plant, pick, then sbr_step).
+ * A BRANCH is j = i*fanout + k: env i, candidate k; there are B = N*fanout of them.
+ *   actions     [ceil(n_steps / hold)][B][2] ActT, DEVICE pointer - a [rows][N][fanout][2] array has this layout.  Rows are
+ *               held and indexed exactly as in sbr_rollout_actions.
+ *   returns     [B] float64 or NULL: sum of the launch's rewards of the branch, added in call order
+ *   rewards_out [n_steps][B] float64 or NULL: the reward of every call; 0.0 for a call the branch skipped
+ *   best_index  [N] int32 or NULL, best_return [N] float64 or NULL: the winner among each env's `fanout` returns.
+ *               The largest return wins; a NaN return compares as -inf; ties go to the lowest k.  best_return is the winner's
+ *               entry of `returns` as it stands - so if all of an env's returns are NaN: index 0 and best_return = NaN.
+ *               The two are reduced FROM `returns` by a second kernel on the same stream: `returns` must be given whenever
+ *               either of them is (the call owns no memory and allocates none).
+ * Branch j starts from env i's plant and controller record as they are - also in the form sbr_step leaves them - and runs the
+ * calls sbr_rollout_actions would run on an env in that state, in the same order: its returns and rewards are the same bits.
+ * A branch whose episode ends skips its remaining calls; the terminal phases behind the done call are not run (they change
+ * only state that is discarded here; the end-of-cycle reward of reward_kind 2 is part of the done call and is included).
+ * NOTHING of the handle is written: the plant, every controller row (SBR_C_PLAN and SBR_C_RETURN included) and the trace stay
+ * as they are.  Nothing is allocated (graph-capturable).  The register budget of the launch goes by B, not by N.
+ * n_steps = 0 writes returns = 0, best_index = 0 and best_return = 0 and reads nothing of the state.
+ * SBR_ERR_INVALID, before anything is touched: NULL env; n_steps < 0; hold < 1; fanout < 1; N*fanout >= 2^31; actions NULL
+ * with n_steps > 0; best_index or best_return given while returns is NULL. */
+int sbr_lookahead_actions(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions, double* returns,
+                          double* rewards_out, int32_t* best_index, double* best_return, void* stream);
+
 /* fused rollout in CLOSED loop under the caller's policy: n_steps fused step() calls per env in ONE kernel, the action of a
  * decision call being a small MLP applied to the env's float32 observation, evaluated on the device next to the plant
  * (policy evaluation, evolution strategies and populations, collectors).
