@@ -26,6 +26,11 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _one_or_all(out):
+    """What a method with optional results returns: the tuple, or its only member."""
+    return out if len(out) > 1 else out[0]
+
+
 # the handle of torch's current stream on a device: torch's own fast accessor (an int, no Stream object) where it exists
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
 
@@ -119,14 +124,38 @@ class SbrOSVec:
                       self._dev(influent, torch.float64, (n, _capi.NX)), self._dev(mask, torch.uint8, (n,)))
         return [_ptr(t) for t in self._keep]
 
+    def _as_actions(self, a, shape):
+        """The caller's tensor as it is where the kernels can read it - contiguous, on the device, of the env's action dtype - or
+        a converted copy of `shape`."""
+        if isinstance(a, torch.Tensor) and a.dtype == self.action_dtype and a.is_contiguous() and a.device == self.device:
+            return a
+        return self._dev(a, self.action_dtype, shape)
+
     def _action(self, action, shape):
         """An action as a contiguous device tensor of the env's action dtype and of `shape` = (N, width), kept alive."""
-        a = action if (isinstance(action, torch.Tensor) and action.dtype == self.action_dtype and action.is_contiguous()
-                       and action.device == self.device) else self._dev(action, self.action_dtype, shape)
+        a = self._as_actions(action, shape)
         if a.shape != shape:
             raise ValueError("action must have shape [N,%d]" % shape[1])
         self._keep_a = a
         return a
+
+    def _tape(self, actions, trailing, n_steps, hold):
+        """What rollout_actions and lookahead ask of a tape: `hold` >= 1, the shape (rows,) + `trailing` (None = any size >= 1),
+        enough rows for `n_steps` calls (None = all of them).  Returns (the tape on the device, kept alive; rows; n_steps)."""
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        shape = tuple(getattr(actions, "shape", ()))
+        if not (len(shape) == 1 + len(trailing)
+                and all(int(s) >= 1 if t is None else int(s) == t for s, t in zip(shape[1:], trailing))):
+            raise ValueError("actions must have shape [R,N,K,2] with K >= 1" if None in trailing else "actions must have shape [R,N,2]")
+        rows = int(shape[0])
+        n_steps = rows * hold if n_steps is None else int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must be >= 0")
+        if -(-n_steps // hold) > rows:
+            raise ValueError("%d calls with hold=%d need %d rows of actions, got %d" % (n_steps, hold, -(-n_steps // hold), rows))
+        self._keep_a = self._as_actions(actions, shape)
+        return self._keep_a, rows, n_steps
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -226,19 +255,7 @@ class SbrOSVec:
         float64, with return_rewards=True also the reward of every call [n_steps, N] float64 (0 for a call an env skipped
         because its episode had ended)."""
         hold = int(hold)
-        if hold < 1:
-            raise ValueError("hold must be >= 1")
-        if not (hasattr(actions, "shape") and len(actions.shape) == 3 and tuple(actions.shape[1:]) == self._ashape):
-            raise ValueError("actions must have shape [R,N,2]")
-        rows = int(actions.shape[0])
-        n_steps = rows * hold if n_steps is None else int(n_steps)
-        if n_steps < 0:
-            raise ValueError("n_steps must be >= 0")
-        if -(-n_steps // hold) > rows:
-            raise ValueError("%d calls with hold=%d need %d rows of actions, got %d" % (n_steps, hold, -(-n_steps // hold), rows))
-        a = actions if (isinstance(actions, torch.Tensor) and actions.dtype == self.action_dtype and actions.is_contiguous()
-                        and actions.device == self.device) else self._dev(actions, self.action_dtype, actions.shape)
-        self._keep_a = a
+        a, rows, n_steps = self._tape(actions, self._ashape, n_steps, hold)
         ret = torch.empty((self.num_envs,), dtype=torch.float64, device=self.device)
         rew = torch.empty((n_steps, self.num_envs), dtype=torch.float64, device=self.device) if return_rewards else None
         _capi.check(self.lib.sbr_rollout_actions(self._h, n_steps, hold, _ptr(a) if rows else None, _ptr(ret), _ptr(rew),
@@ -253,20 +270,8 @@ class SbrOSVec:
         float64 (0 for a call a candidate skipped because its episode had ended); with return_best=True also best_index [N]
         int32 and best_return [N] float64: per env the largest return, NaN counting as -inf, ties to the lowest index."""
         hold = int(hold)
-        if hold < 1:
-            raise ValueError("hold must be >= 1")
-        if not (hasattr(actions, "shape") and len(actions.shape) == 4 and int(actions.shape[1]) == self.num_envs
-                and int(actions.shape[2]) >= 1 and int(actions.shape[3]) == 2):
-            raise ValueError("actions must have shape [R,N,K,2] with K >= 1")
-        rows, fanout = int(actions.shape[0]), int(actions.shape[2])
-        n_steps = rows * hold if n_steps is None else int(n_steps)
-        if n_steps < 0:
-            raise ValueError("n_steps must be >= 0")
-        if -(-n_steps // hold) > rows:
-            raise ValueError("%d calls with hold=%d need %d rows of actions, got %d" % (n_steps, hold, -(-n_steps // hold), rows))
-        a = actions if (isinstance(actions, torch.Tensor) and actions.dtype == self.action_dtype and actions.is_contiguous()
-                        and actions.device == self.device) else self._dev(actions, self.action_dtype, actions.shape)
-        self._keep_a = a
+        a, rows, n_steps = self._tape(actions, (self.num_envs, None, 2), n_steps, hold)
+        fanout = int(a.shape[2])
         n, dev = self.num_envs, self.device
         ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
         rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
@@ -274,8 +279,7 @@ class SbrOSVec:
         br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
         _capi.check(self.lib.sbr_lookahead_actions(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, _ptr(ret), _ptr(rew),
                                                    _ptr(bi), _ptr(br), self._stream()), self._h)
-        out = (ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ())
-        return out if len(out) > 1 else ret
+        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ()))
 
     def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
                        return_rewards=False):
@@ -311,8 +315,7 @@ class SbrOSVec:
         if own and o is not self.obs:        # a float64 handle: the rows of the envs that are not done come back, the others stay
             live = self.ctrl_row(_capi.C_DONE) == 0
             self.obs.copy_(torch.where(live[:, None], o.to(self.obs.dtype), self.obs))
-        out = (ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ())
-        return out if len(out) > 1 else ret
+        return _one_or_all((ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ()))
 
     def enable_trace(self, n_envs=1, capacity=463):
         """Trajectory export: every step() appends one record (_capi.TR_*: t, x(14), Kla, EC, reward, done, the set-points in

@@ -1,111 +1,26 @@
 """Static checks of the gfx950 ISA that hipcc generates for the stepping kernels (cross-compiled here, no GPU needed):
 the figures DESIGN.md and bench.py quote - float64 operations per RK4 substep, no IEEE division on the ordinary path, no
 scratch, two waves per SIMD - are asserted against the compiler's output, so that they cannot drift from the code."""
-import collections
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 from conftest import ROOT
+from isa import (K_CYCLE, K_CYCLE_RESET, K_CYCLE_RK4, K_RESET, K_RESET_CARRY, K_RESET_WIDE, K_ROLLOUT, K_ROLLOUT_2W, K_ROLLOUT_RK4,
+                 K_STEP, K_STEP_2W, K_STEP_RK4, K_STEP_SMALL, b5_steps, f64_mix, flop_counts, instructions, kernel_text, library_asm,
+                 meta, rk4_loops)
 
 from gym_sbr2_amd import build as B
 
-K_STEP = "_Z6k_stepIffLi256ELb0ELi1ELi1EE"  # k_step<float, float, 256, false, 1, 1>: the kernel bench.py times (scheme 1)
-K_STEP_SMALL = "_Z6k_stepIffLi64ELb0ELi1ELi1EE"    # the 64-thread-workgroup build used up to 49152 envs
-K_STEP_RK4 = "_Z6k_stepIffLi256ELb0ELi0ELi1EE"   # cfg.scheme = 0: ten RK4 substeps per interval
-K_STEP_2W = "_Z6k_stepIffLi256ELb0ELi1ELi2EE"  # the same above 65536 envs: parked call state, two waves per SIMD
-K_ROLLOUT = "_Z9k_rolloutILb0ELi1ELi1EE"      # k_rollout<false, 1, 1>: scheme 1, register budget for one wave per SIMD
-K_ROLLOUT_2W = "_Z9k_rolloutILb0ELi1ELi2EE"
-K_ROLLOUT_RK4 = "_Z9k_rolloutILb0ELi0ELi2EE"
-K_CYCLE = "_Z7k_cycleIffLi1ELi1EE"
-K_CYCLE_RK4 = "_Z7k_cycleIffLi0ELi2EE"
-K_RESET = "_Z7k_resetIfLb0ELi256EE"
-K_RESET_CARRY = "_Z7k_resetIfLb1ELi256EE"
-K_RESET_WIDE = "_Z7k_resetIfLb0ELi512EE"      # above one wave per SIMD: 512-thread workgroups (one 84 KiB table copy per CU, two waves per SIMD)
-K_CYCLE_RESET = "_Z13k_cycle_resetIfLb0EE"
-
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa") / "sbr_amd.s"
-    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
-    subprocess.check_call([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", str(out), B.SRC], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def kernel_text(asm, symbol):
-    m = re.search(r"^%s[^\n:]*:[^\n]*\n(.*?)\n\.Lfunc_end" % re.escape(symbol), asm, re.S | re.M)
-    assert m, symbol
-    return m.group(1)
-
-
-def instructions(text):
-    out = []
-    for line in text.split("\n"):
-        line = line.split(";")[0].strip()
-        if line and not line.endswith(":") and not line.startswith("."):
-            out.append(line)
-    return out
-
-
-def inner_loops(text):
-    """[(instruction list)] of the innermost loops (backward branches that contain no other backward branch)."""
-    lines = []
-    for raw in text.split("\n"):
-        l = raw.split(";")[0].strip()
-        if l and (l.endswith(":") or not l.startswith(".")):
-            lines.append(l)
-    label = {l[:-1]: i for i, l in enumerate(lines) if l.endswith(":")}
-    loops = []
-    for i, l in enumerate(lines):
-        m = re.match(r"s_(?:cbranch_\w+|branch)\s+(\.LBB\S+)", l)
-        if m and m.group(1) in label and label[m.group(1)] < i:
-            loops.append((label[m.group(1)], i))
-    inner = [lp for lp in loops if not any(o != lp and lp[0] <= o[0] and o[1] <= lp[1] for o in loops)]
-    return [[x for x in lines[a:b + 1] if not x.endswith(":")] for a, b in inner]
-
-
-def all_loops(text):
-    """[(instruction list)] of EVERY loop (one per backward branch, label to branch), nested or not."""
-    lines = []
-    for raw in text.split("\n"):
-        l = raw.split(";")[0].strip()
-        if l and (l.endswith(":") or not l.startswith(".")):
-            lines.append(l)
-    label = {l[:-1]: i for i, l in enumerate(lines) if l.endswith(":")}
-    out = []
-    for i, l in enumerate(lines):
-        m = re.match(r"s_(?:cbranch_\w+|branch)\s+(\.LBB\S+)", l)
-        if m and m.group(1) in label and label[m.group(1)] < i:
-            out.append([x for x in lines[label[m.group(1)]:i + 1] if not x.endswith(":")])
-    return out
-
-
-def f64_mix(ins):
-    c = collections.Counter(i.split()[0] for i in ins)
-    return {"fma": c["v_fma_f64"] + c["v_fmac_f64_e32"], "mul": c["v_mul_f64"], "add": c["v_add_f64"], "rcp": c["v_rcp_f64_e32"],
-            "div": c["v_div_fmas_f64"], "lane": c["v_readlane_b32"] + c["v_writelane_b32"], "scratch": sum(v for k, v in c.items() if k.startswith("scratch_"))}
-
-
-def meta(asm, symbol, key):
-    """A field of the kernel's entry in the code object's metadata (amdhsa.kernels).  The entries are YAML maps whose keys are
-    sorted, so some precede `.name` and some follow it: take the whole entry (it starts at `  - .agpr_count:`)."""
-    for blk in re.split(r"\n  - (?=\.agpr_count:)", asm[asm.index("amdhsa.kernels:"):]):
-        if re.search(r"\.name:\s+%s\S*\n" % re.escape(symbol), blk):
-            m = re.search(r"^\s+\.%s:\s+(\d+)" % key, "\n    " + blk, re.M)
-            assert m, (symbol, key)
-            return int(m.group(1))
-    raise AssertionError((symbol, "not in the metadata"))
+def asm():
+    return library_asm()
 
 
 def test_rk4_substep_loops_have_the_quoted_instruction_mix(asm):
     import bench
-    loops = inner_loops(kernel_text(asm, K_STEP_RK4))             # cfg.scheme = 0
-    rk4 = [f64_mix(l) for l in loops if f64_mix(l)["rcp"] == 8 and f64_mix(l)["fma"] > 250]     # unrolled by two: 8 reciprocals
+    loops = rk4_loops(kernel_text(asm, K_STEP_RK4))               # cfg.scheme = 0; unrolled by two: 8 reciprocals
+    rk4 = [f64_mix(l) for l in loops]
     # (the Butcher-5 step loops of scheme 1 hold 5 reciprocals: test_butcher5_step_loops below)
     assert len(rk4) >= 2
     per_substep = sorted({(m["fma"] * 2 + m["mul"] + m["add"] + m["rcp"]) // 2 for m in rk4})
@@ -113,13 +28,12 @@ def test_rk4_substep_loops_have_the_quoted_instruction_mix(asm):
     assert per_substep[0] == bench.FP64_FLOP_PER_SUBSTEP["plain"] and per_substep[-1] == bench.FP64_FLOP_PER_SUBSTEP["dosing"], per_substep
     # the dosing loop in scaled-mass variables - at most 310 instructions per substep (measured 296.5;
     # the concentration form of rounds 2-3 had 343.5), the closed loop unchanged at 275
-    per_substep_instr = sorted(len(l) / 2.0 for l in loops if f64_mix(l)["rcp"] == 8 and f64_mix(l)["fma"] > 250)
+    per_substep_instr = sorted(len(l) / 2.0 for l in loops)
     assert per_substep_instr[-1] <= 310 and per_substep_instr[0] <= 276, per_substep_instr
     for l in loops:
         m = f64_mix(l)
-        if m["rcp"] == 8 and m["fma"] > 250:
-            assert m["div"] == 0 and m["lane"] == 0 and m["scratch"] == 0       # nothing but arithmetic in the hot loops
-            assert len(l) <= 2 * (m["fma"] + m["mul"] + m["add"] + m["rcp"]) // 2 + 12   # <= 6 non-arithmetic instructions per substep
+        assert m["div"] == 0 and m["lane"] == 0 and m["scratch"] == 0       # nothing but arithmetic in the hot loops
+        assert len(l) <= 2 * (m["fma"] + m["mul"] + m["add"] + m["rcp"]) // 2 + 12   # <= 6 non-arithmetic instructions per substep
 
 
 def test_butcher5_step_loops(asm):
@@ -133,9 +47,9 @@ def test_butcher5_step_loops(asm):
     for k in (K_STEP, K_STEP_2W, K_ROLLOUT, K_CYCLE):
         # (lane operations in a step loop are SGPR spills into VGPR lanes: none in k_step and k_cycle, the one-wave build of
         # k_rollout holds four per step since the library is built with -ffp-contract=off - under 1 % of the loop)
-        steps = [l for l in all_loops(kernel_text(asm, k)) if f64_mix(l)["rcp"] == 6 and len(l) < 580 and f64_mix(l)["lane"] <= (4 if k == K_ROLLOUT else 0)]
+        steps = [l for l in b5_steps(kernel_text(asm, k)) if f64_mix(l)["lane"] <= (4 if k == K_ROLLOUT else 0)]
         assert len(steps) >= (1 if k == K_CYCLE else 2), k
-        flop = sorted({m["fma"] * 2 + m["mul"] + m["add"] + m["rcp"] for m in map(f64_mix, steps)})
+        flop = flop_counts(steps)
         assert flop[0] == bench.FP64_FLOP_PER_B5_STEP["plain"], (k, flop)
         if k != K_CYCLE:
             assert flop[-1] == bench.FP64_FLOP_PER_B5_STEP["dosing"], (k, flop)
@@ -150,7 +64,7 @@ def test_butcher5_step_loops(asm):
         assert sum(1 for l in steps if not any("accvgpr" in i for i in l)) >= (1 if k == K_CYCLE else 2), k
     # the scheme-1 kernels carry no RK4 loop for the control intervals (k_step's only RK4 is gone with the idle phase; k_cycle
     # keeps the fill phase's), the scheme-0 kernels are what rounds 1-4 shipped
-    rk4 = lambda k: [l for l in inner_loops(kernel_text(asm, k)) if f64_mix(l)["rcp"] == 8 and f64_mix(l)["fma"] > 250]   # noqa: E731
+    rk4 = lambda k: rk4_loops(kernel_text(asm, k))   # noqa: E731
     assert len(rk4(K_STEP)) == 0 and len(rk4(K_ROLLOUT)) == 0 and len(rk4(K_STEP_RK4)) >= 2 and len(rk4(K_ROLLOUT_RK4)) >= 2
     assert len(instructions(kernel_text(asm, K_STEP))) < 0.8 * 11200      # 7 614 instructions; 11 142 with both schemes in one kernel
 
@@ -210,15 +124,6 @@ def test_secondary_kernels_carry_no_ieee_divisions(asm):
     assert meta(asm, K_ROLLOUT, "vgpr_count") <= 320
 
 
-def _lines_with_comments(text):
-    out = []
-    for raw in text.split("\n"):
-        l = raw.split(";")[0].strip()
-        if l and not l.startswith(".") and not l.endswith(":"):
-            out.append(l)
-    return out
-
-
 VALU_PREFIX = ("v_",)       # everything the vector ALU executes; VMEM (global_/buffer_/scratch_), LDS (ds_), SALU (s_) are not
 
 
@@ -232,7 +137,7 @@ def test_inline_asm_invariants(asm, kernel):
           paired-rows patch: a memory-access fault) - every asm store uses the VGPR-address form `..., off`;
       (c) a kernarg warm-up load (SBR_WARM_LINES) past the end of the kernel's argument segment."""
     text = kernel_text(asm, kernel)
-    ins = _lines_with_comments(text)
+    ins = instructions(text)
     wide_sc1 = [i for i, l in enumerate(ins) if l.startswith("global_store_dwordx4") and "sc1" in l]
     if kernel in (K_STEP, K_STEP_2W, K_STEP_SMALL, K_STEP_RK4):
         assert len(wide_sc1) >= 9                      # the output rows leave as 16-byte write-through stores

@@ -5,22 +5,13 @@ one-wave build, nothing but arithmetic in the Butcher-5 step loops - and holds n
 14 + 25 rows of the handle, this one writes none of them (tests/test_lookahead_gpu.py decides "read-only" on the device)."""
 import ctypes as C
 import inspect
-import os
-import shutil
-import subprocess
 
 import pytest
 from conftest import ROOT  # noqa: F401  (puts the repository root on sys.path)
-from test_isa_cpu import f64_mix, instructions, kernel_text, meta
-from test_tape_rollout_cpu import K_TAPE, _b5_steps
+from isa import (K_LOOK, K_LOOK_2W, K_LOOK_RK4, K_TAPE, b5_steps, f64_mix, flop_counts, instructions, kernel_text, library_asm, meta,
+                 vector_stores as _vector_stores)
 
 from gym_sbr2_amd import _capi
-from gym_sbr2_amd import build as B
-
-# k_lookahead_tape<float, false, SCH, WAVES>: the float32 tape, the SBROS-v1 reward
-K_LOOK = "_Z16k_lookahead_tapeIfLb0ELi1ELi1EE"       # scheme 1, register budget for one wave per SIMD (up to 98 304 branches)
-K_LOOK_2W = "_Z16k_lookahead_tapeIfLb0ELi1ELi2EE"    # scheme 1, two waves per SIMD
-K_LOOK_RK4 = "_Z16k_lookahead_tapeIfLb0ELi0ELi2EE"   # scheme 0, two waves per SIMD
 
 
 def test_symbol_is_exported_and_bound():
@@ -71,17 +62,8 @@ def test_python_surface_exists():
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa_lookahead") / "sbr_amd.s"
-    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
-    subprocess.check_call([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", str(out), B.SRC], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def _vector_stores(asm, symbol):
-    return [i for i in instructions(kernel_text(asm, symbol)) if i.split()[0].startswith(("global_store", "flat_store", "buffer_store"))]
+def asm():
+    return library_asm()
 
 
 def test_lookahead_kernel_register_budgets_and_scratch(asm):
@@ -95,9 +77,9 @@ def test_lookahead_kernel_register_budgets_and_scratch(asm):
 def test_lookahead_kernel_step_loops(asm):
     import bench
     for k in (K_LOOK, K_LOOK_2W):
-        steps = _b5_steps(kernel_text(asm, k))
+        steps = b5_steps(kernel_text(asm, k))
         assert len(steps) >= 2, k
-        flop = sorted({m["fma"] * 2 + m["mul"] + m["add"] + m["rcp"] for m in map(f64_mix, steps)})
+        flop = flop_counts(steps)
         assert flop[0] == bench.FP64_FLOP_PER_B5_STEP["plain"] and flop[-1] == bench.FP64_FLOP_PER_B5_STEP["dosing"], (k, flop)
         for l in steps:
             m = f64_mix(l)

@@ -17,18 +17,15 @@ The other seven builds differ from these in template arguments the kernel only p
 (tests/test_tape_rollout_gpu.py runs those under every argument) and are not run here."""
 import numpy as np
 import pytest
+from gpu_common import STEPS, package
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-STEPS = 463                     # calls of one SBROS-v1 episode
-
 
 @pytest.fixture(scope="module")
 def G():
-    import gym_sbr2_amd
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    return gym_sbr2_amd
+    return package()
 
 
 def _live(G, n, calls, seed, **kw):

@@ -5,22 +5,13 @@ registers in the others, nothing but the tape kernel's arithmetic in the Butcher
 import collections
 import ctypes as C
 import inspect
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 from conftest import ROOT  # noqa: F401  (puts the repository root on sys.path)
-from test_isa_cpu import all_loops, f64_mix, instructions, kernel_text, meta
-from test_tape_rollout_cpu import K_TAPE, K_TAPE_2W
+from isa import K_POL, K_TAPE, K_TAPE_2W, b5_steps, f64_mix, flop_counts, instructions, kernel_text, library_asm, meta
 
 from gym_sbr2_amd import _capi
-from gym_sbr2_amd import build as B
-
-# k_rollout_policy<H, false, SCH, WAVES>: the SBROS-v1 reward
-K_POL = {(h, sch, wv): "_Z16k_rollout_policyILi%dELb0ELi%dELi%dEE" % (h, sch, wv)
-         for h in (32, 64) for sch, wv in ((1, 1), (1, 2), (0, 2))}
 
 
 def _policy(**kw):
@@ -205,18 +196,8 @@ def test_python_surface_exists():
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa_policy") / "sbr_amd.s"
-    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
-    subprocess.check_call([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", str(out), B.SRC], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def _b5_steps(text):
-    """The Butcher-5 step loops: six reciprocals, and no loop nested inside (a loop around a whole call holds dozens)."""
-    return [l for l in all_loops(text) if f64_mix(l)["rcp"] == 6 and len(l) < 700]
+def asm():
+    return library_asm()
 
 
 def test_policy_kernel_register_budgets_and_scratch(asm):
@@ -230,14 +211,14 @@ def test_policy_kernel_register_budgets_and_scratch(asm):
 
 def test_policy_kernel_step_loops_are_the_tape_kernels(asm):
     import bench
-    tape_scratch = {1: max(f64_mix(l)["scratch"] for l in _b5_steps(kernel_text(asm, K_TAPE))),
-                    2: max(f64_mix(l)["scratch"] for l in _b5_steps(kernel_text(asm, K_TAPE_2W)))}
+    tape_scratch = {1: max(f64_mix(l)["scratch"] for l in b5_steps(kernel_text(asm, K_TAPE), 700)),
+                    2: max(f64_mix(l)["scratch"] for l in b5_steps(kernel_text(asm, K_TAPE_2W), 700))}
     for h in (32, 64):
         for wv in (1, 2):
             k = K_POL[h, 1, wv]
-            steps = _b5_steps(kernel_text(asm, k))
+            steps = b5_steps(kernel_text(asm, k), 700)
             assert len(steps) >= 2, k
-            flop = sorted({m["fma"] * 2 + m["mul"] + m["add"] + m["rcp"] for m in map(f64_mix, steps)})
+            flop = flop_counts(steps)
             assert flop[0] == bench.FP64_FLOP_PER_B5_STEP["plain"] and flop[-1] == bench.FP64_FLOP_PER_B5_STEP["dosing"], (k, flop)
             for l in steps:
                 m = f64_mix(l)

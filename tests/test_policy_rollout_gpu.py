@@ -31,39 +31,20 @@ Which test runs which build of k_rollout_policy<H, OCI, SCH, WAVES> (the host pi
   (64, no, 1, 2)  test_two_waves_build_above_98304_envs_matches_small_handles (its second half)
   (32, yes, 1, 2), (64, no, 0, 2) and the three (64, yes, ...) builds are not run by any test.
 pl.squash == 0: test_squash_none; every other test squashes with tanh."""
-import os
-
 import numpy as np
 import pytest
+from gpu_common import CONFIGS, FLAGS, STEPS, handle as _handle, inputs as _inputs, no_flags, package, to_np as _np
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-STEPS = 463                     # calls of one SBROS-v1 episode
-FLAGS = 1 | 2 | 4               # SBR_ST_NEGATIVE | SBR_ST_NEAR_POLE | SBR_ST_NONFINITE
 LOW, HIGH = (0.0, 0.0), (2.5, 15.0)
 U = 2.0 ** -24
 
 
 @pytest.fixture(scope="module")
 def G():
-    import gym_sbr2_amd
-    from gym_sbr2_amd import _capi
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    lib = _capi.load()
-    assert _capi.library_path().endswith(os.path.join("gym_sbr2_amd", "lib", "libsbr_amd.so"))   # the in-tree .so is what runs
-    assert lib.sbr_device_count() >= 1
-    return gym_sbr2_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _inputs(n, seed, first=0):
-    rs = np.random.RandomState(seed)
-    scen = (4 + (first + np.arange(n)) % 4).astype(np.int32)
-    return scen, rs.randn(n, 48)
+    return package()
 
 
 def _net(seed, widths):
@@ -96,8 +77,7 @@ def _same_state(a, b, cols=slice(None)):
 
 def _no_flags(env):
     from gym_sbr2_amd import _capi
-    st = _np(env.ctrl_row(_capi.C_STATUS)).astype(np.int64)
-    assert np.count_nonzero(st & FLAGS) == 0, "%d envs flagged" % np.count_nonzero(st & FLAGS)
+    no_flags(env.ctrl_row(_capi.C_STATUS))
 
 
 def _bound(pol, o, member=0):
@@ -301,9 +281,6 @@ def test_squash_none(G):
     assert worst <= 1.0
 
 
-CONFIGS = [(0, "eqi_oci"), (1, "g2anet"), (1, "oci"), (0, "oci")]
-
-
 @pytest.mark.parametrize("scheme,reward", CONFIGS)
 def test_schemes_and_rewards_against_the_tape_kernel(G, scheme, reward):
     """The policy builds behind a non-default config - scheme 0 (RK4 x substeps, always the two-waves build), the G2ANET reward (a
@@ -319,9 +296,8 @@ def test_schemes_and_rewards_against_the_tape_kernel(G, scheme, reward):
     pol = _policy(13, (32, 32))
 
     def handle():
-        cfg = _capi.default_config(); cfg.scheme = scheme
-        env = _env(G, n, inputs, config=cfg, reward=reward)
-        assert env.cfg.scheme == scheme and env.cfg.reward_kind == _capi.REWARD_KINDS[reward]
+        env = _handle(G, n, scheme, reward)
+        env.reset(scenario=inputs[0], rnd=inputs[1])
         return env
 
     a_env, b_env = handle(), handle()

@@ -2,21 +2,13 @@
 kernel (k_rollout_tape, cross-compiled as tests/test_isa_cpu.py does) keeps what is asserted there for k_rollout - register
 budgets, no scratch in the one-wave build, nothing but arithmetic in the Butcher-5 step loops."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import pytest
 from conftest import ROOT  # noqa: F401  (puts the repository root on sys.path)
-from test_isa_cpu import all_loops, f64_mix, inner_loops, instructions, kernel_text, meta
+from isa import (K_ROLLOUT, K_TAPE, K_TAPE_2W, K_TAPE_F64, K_TAPE_RK4, b5_steps, f64_mix, flop_counts, instructions, kernel_text,
+                 library_asm, meta, rk4_loops)
 
 from gym_sbr2_amd import _capi
-from gym_sbr2_amd import build as B
-
-# k_rollout_tape<float, false, SCH, WAVES>: the float32 tape, the SBROS-v1 reward
-K_TAPE = "_Z14k_rollout_tapeIfLb0ELi1ELi1EE"        # scheme 1, register budget for one wave per SIMD (up to 98 304 envs)
-K_TAPE_2W = "_Z14k_rollout_tapeIfLb0ELi1ELi2EE"     # scheme 1, two waves per SIMD
-K_TAPE_RK4 = "_Z14k_rollout_tapeIfLb0ELi0ELi2EE"    # scheme 0, two waves per SIMD
 
 
 def test_symbol_is_exported_and_bad_arguments_are_refused_without_a_device():
@@ -44,18 +36,8 @@ def test_python_surface_exists():
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("isa_tape") / "sbr_amd.s"
-    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
-    subprocess.check_call([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", str(out), B.SRC], stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def _b5_steps(text):
-    """The Butcher-5 step loops, picked as tests/test_isa_cpu.py::test_butcher5_step_loops picks them: six reciprocals."""
-    return [l for l in all_loops(text) if f64_mix(l)["rcp"] == 6 and len(l) < 580]
+def asm():
+    return library_asm()
 
 
 def test_tape_kernel_register_budgets_and_scratch(asm):
@@ -70,16 +52,16 @@ def test_tape_kernel_step_loops(asm):
     import bench
     text = kernel_text(asm, K_TAPE)
     # scheme 1 carries no RK4 loop for the control intervals; scheme 0 keeps its two
-    rk4 = lambda k: [l for l in inner_loops(kernel_text(asm, k)) if f64_mix(l)["rcp"] == 8 and f64_mix(l)["fma"] > 250]   # noqa: E731
+    rk4 = lambda k: rk4_loops(kernel_text(asm, k))   # noqa: E731
     assert len(rk4(K_TAPE)) == 0 and len(rk4(K_TAPE_2W)) == 0 and len(rk4(K_TAPE_RK4)) >= 2
     for k in (K_TAPE, K_TAPE_2W):
-        steps = _b5_steps(kernel_text(asm, k))
+        steps = b5_steps(kernel_text(asm, k))
         assert len(steps) >= 2, k
-        flop = sorted({m["fma"] * 2 + m["mul"] + m["add"] + m["rcp"] for m in map(f64_mix, steps)})
+        flop = flop_counts(steps)
         assert flop[0] == bench.FP64_FLOP_PER_B5_STEP["plain"] and flop[-1] == bench.FP64_FLOP_PER_B5_STEP["dosing"], (k, flop)
         for l in steps:
             assert f64_mix(l)["div"] == 0, k                       # no v_div_fmas_f64 in any step loop
-    for l in _b5_steps(text):
+    for l in b5_steps(text):
         m = f64_mix(l)
         arith = m["fma"] + m["mul"] + m["add"] + m["rcp"]
         assert arith in (477, 537) and len(l) <= arith + 45 and m["scratch"] == 0 and m["lane"] <= 4, (len(l), m)
@@ -90,6 +72,6 @@ def test_tape_reads_are_one_load_per_lane_and_row(asm):
     k_rollout, which reads the same rows of the handle, the tape kernel holds exactly two more loads - the first row before
     the loop over the calls, the next row inside it."""
     loads = lambda k, op: sum(1 for i in instructions(kernel_text(asm, k)) if i.split()[0] == op)   # noqa: E731
-    assert loads(K_TAPE, "global_load_dwordx2") == loads("_Z9k_rolloutILb0ELi1ELi1EE", "global_load_dwordx2") + 2
+    assert loads(K_TAPE, "global_load_dwordx2") == loads(K_ROLLOUT, "global_load_dwordx2") + 2
     assert loads(K_TAPE, "global_load_dword") == 0 and loads(K_TAPE, "flat_load_dwordx2") == 0
-    assert loads("_Z14k_rollout_tapeIdLb0ELi1ELi1EE", "global_load_dwordx4") == 2
+    assert loads(K_TAPE_F64, "global_load_dwordx4") == 2

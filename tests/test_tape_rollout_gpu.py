@@ -21,43 +21,20 @@ Which test runs which build of k_rollout_tape<ActT, OCI, SCH, WAVES> (the host p
   (f64, no, 1, 1), their plant and reward in the float32 builds of the same config.  (f32, yes, 1, 2), (f64, no, 1, 2) and
   (f64, yes, 1, 2) are not run by any test.
 tests/test_policy_rollout_gpu.py runs the f32 builds of the four non-default configs once more, on a policy's actions."""
-import os
-
 import numpy as np
 import pytest
 from conftest import gate
+from gpu_common import CONFIGS, FLAGS, STEPS, handle as _handle, inputs as _inputs, no_flags, package, to_np as _np
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from oracle import sbr_oracle as O  # noqa: E402  (the checker, never the thing under test)
 
-STEPS = 463                     # calls of one SBROS-v1 episode
-FLAGS = 1 | 2 | 4               # SBR_ST_NEGATIVE | SBR_ST_NEAR_POLE | SBR_ST_NONFINITE
-
 
 @pytest.fixture(scope="module")
 def G():
-    import gym_sbr2_amd
-    from gym_sbr2_amd import _capi
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    lib = _capi.load()
-    assert _capi.library_path().endswith(os.path.join("gym_sbr2_amd", "lib", "libsbr_amd.so"))   # the in-tree .so is what runs
-    assert lib.sbr_device_count() >= 1
-    return gym_sbr2_amd
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _inputs(n, rows, seed, first=0):
-    """scenario [n] int32, rnd [n, 48] float64, tape [rows, n, 2] float32 for the envs with global ids first .. first + n - 1."""
-    rs = np.random.RandomState(seed)
-    scen = (4 + (first + np.arange(n)) % 4).astype(np.int32)
-    rnd = rs.randn(n, 48)
-    tape = np.stack([rs.uniform(0, 2.5, (rows, n)), rs.uniform(0, 15, (rows, n))], axis=-1).astype(np.float32)
-    return scen, rnd, tape
+    return package()
 
 
 def _state(env):
@@ -67,8 +44,7 @@ def _state(env):
 
 def _no_flags(ctrl):
     from gym_sbr2_amd import _capi
-    st = _np(ctrl[_capi.C_STATUS]).astype(np.int64)
-    assert np.count_nonzero(st & FLAGS) == 0, "%d envs flagged" % np.count_nonzero(st & FLAGS)
+    no_flags(ctrl[_capi.C_STATUS])
 
 
 def test_bad_arguments_are_refused_on_a_live_handle(G):
@@ -102,7 +78,7 @@ def test_same_bits_as_sbr_rollout_on_its_sampled_actions(G, tape_dtype):
     policy over the whole action box leaves the model's domain on most envs; bit equality does not care.)"""
     from gym_sbr2_amd import _capi
     n = 512
-    scen, rnd, _ = _inputs(n, 1, seed=101, first=1000)
+    scen, rnd, _ = _inputs(n, seed=101, first=1000, rows=1)
     dt = getattr(torch, tape_dtype)
     a_env = G.SbrOSVec(n, first_env_id=1000)
     b_env = G.SbrOSVec(n, first_env_id=1000, action_dtype=dt)
@@ -122,7 +98,7 @@ def test_equals_sbr_step_and_the_oracle_on_the_callers_tape(G, tables):
     from gym_sbr2_amd import _capi
     means, stds = tables
     n = 512
-    scen, rnd, tape = _inputs(n, STEPS, seed=202)
+    scen, rnd, tape = _inputs(n, seed=202, rows=STEPS)
     t_env = G.SbrOSVec(n)
     s_env = G.SbrOSVec(n, out_dtype=torch.float64)
     t_env.reset(scenario=scen, rnd=rnd); s_env.reset(scenario=scen, rnd=rnd)
@@ -170,17 +146,7 @@ def test_equals_sbr_step_and_the_oracle_on_the_callers_tape(G, tables):
     t_env.close(); s_env.close()
 
 
-CONFIGS = [(0, "eqi_oci"), (1, "g2anet"), (1, "oci"), (0, "oci")]
 OCI_COEF = 8.000000000006622 / 1800 * 1.32 * (0.002 / 24)      # d(end-of-cycle reward) / d(sum(Kla)), test_gpu_parity.py::test_oci_reward_option
-
-
-def _handle(G, n, scheme, reward, **kw):
-    from gym_sbr2_amd import _capi
-    cfg = _capi.default_config(); cfg.scheme = scheme
-    env = G.SbrOSVec(n, config=cfg, reward=reward, **kw)
-    assert env.cfg.scheme == scheme and env.cfg.reward_kind == _capi.REWARD_KINDS[reward]
-    assert env.query(_capi.Q_ROLLOUT_WAVES) == (2 if scheme == 0 else 1)
-    return env
 
 
 @pytest.mark.parametrize("scheme,reward", CONFIGS)
@@ -210,7 +176,7 @@ def test_schemes_and_rewards_equal_sbr_step_and_the_oracle(G, tables, scheme, re
     means, stds = tables
     n = 256
     oci = reward == "oci"
-    scen, rnd, tape = _inputs(n, STEPS, seed=202)
+    scen, rnd, tape = _inputs(n, seed=202, rows=STEPS)
     t_env = _handle(G, n, scheme, reward)
     s_env = _handle(G, n, scheme, reward, out_dtype=torch.float64)
     t_env.reset(scenario=scen, rnd=rnd); s_env.reset(scenario=scen, rnd=rnd)
@@ -285,7 +251,7 @@ def test_float64_tape_in_the_scheme_0_oci_build(G):
     kernels cast the lane's pair to double before anything else, and float32 -> float64 is exact.)"""
     from gym_sbr2_amd import _capi
     n = 256
-    scen, rnd, tape = _inputs(n, STEPS, seed=202)
+    scen, rnd, tape = _inputs(n, seed=202, rows=STEPS)
     e32 = _handle(G, n, 0, "oci")
     e64 = _handle(G, n, 0, "oci", action_dtype=torch.float64)
     assert e64.cfg.act_f64 == 1 and e32.cfg.act_f64 == 0
@@ -310,7 +276,7 @@ def test_hold_and_split_launches(G):
     n, hold = 512, 8
     rows = -(-STEPS // hold)
     assert rows == 58
-    scen, rnd, short = _inputs(n, rows, seed=303)
+    scen, rnd, short = _inputs(n, seed=303, rows=rows)
     long_tape = torch.from_numpy(np.repeat(short, hold, axis=0)[:STEPS].copy()).cuda()
     short = torch.from_numpy(short).cuda()
     env = G.SbrOSVec(n)
@@ -364,7 +330,7 @@ def test_an_envs_result_does_not_depend_on_the_batch_around_it(G):
     other lanes and other workgroups) and against a rank of a sharded batch, each fed its slice of the tape: bit for bit."""
     from gym_sbr2_amd import ShardedSbrOS, _capi
     n, lo, hi = 4096, 1000, 2024
-    scen, rnd, tape = _inputs(n, STEPS, seed=404)
+    scen, rnd, tape = _inputs(n, seed=404, rows=STEPS)
     tape = torch.from_numpy(tape).cuda()
     big = G.SbrOSVec(n)
     big.reset(scenario=scen, rnd=rnd)
@@ -395,7 +361,7 @@ def test_two_waves_build_above_98304_envs_matches_small_handles(G):
     98 624; bit equality between the two builds does not care, so nothing is asserted about the flags here.)"""
     from gym_sbr2_amd import _capi
     n, hold = 98304 + 320, 8                           # not a multiple of 256: the last workgroup is ragged
-    scen, rnd, tape = _inputs(n, 58, seed=505)
+    scen, rnd, tape = _inputs(n, seed=505, rows=58)
     tape = torch.from_numpy(tape).cuda()
     env = G.SbrOSVec(n)
     assert env.query(_capi.Q_ROLLOUT_WAVES) == 2
