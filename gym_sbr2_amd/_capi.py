@@ -53,6 +53,12 @@ class SbrPolicy(C.Structure):
                 ("noise_seed", C.c_uint64)]
 
 
+class SbrSampler(C.Structure):
+    """struct sbr_sampler of include/sbr_amd.h (sbr_lookahead_sampled, sbr_mppi_update)."""
+    _fields_ = [("sigma", C.c_float * 2), ("lo", C.c_float * 2), ("hi", C.c_float * 2), ("seed", C.c_uint64),
+                ("keep_nominal", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class SbrError(RuntimeError):
     pass
 
@@ -80,6 +86,8 @@ SYMBOLS = {
     "sbr_rollout": (C.c_int, [_VP, _I32, _U64, _VP, _VP, _VP]),
     "sbr_rollout_actions": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_actions": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_lookahead_sampled": (C.c_int, [_VP, _I32, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_mppi_update": (C.c_int, [_VP, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, C.c_double, _I32, _VP, _VP, _VP]),
     "sbr_policy_param_count": (_I64, [_I32, _I32]),
     "sbr_rollout_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP]),
     "sbr_reduce_stats": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),

@@ -1224,3 +1224,25 @@ SBR_DEV void sbr_policy_action(const SbrPar& p, uint64_t seed, uint64_t env_id, 
     a0 = (float)(sbr_u53(c[0], c[1]) * p.act_DO_max);
     a1 = (float)(sbr_u53(c[2], c[3]) * p.act_EC_max);
 }
+
+// THE SAMPLE of sbr_lookahead_sampled / sbr_mppi_update (include/sbr_amd.h): candidate k of the env with global id `gid` at the
+// launch-relative row r, around the nominal pair (m0, m1).  One Box-Muller pair of Philox stream 4 (sbr_normal_pair's
+// construction; streams 0 - 3 are the influent, the random policy, the scenario draw and the policy noise), k in the upper 24 bits
+// of the stream word.  Written once: the lane that integrates the candidate and the update that averages it call this function,
+// and under -ffp-contract=off the same operations give the same bits in both.
+template <typename ActT>
+SBR_DEV void sbr_tape_sample(const sbr_sampler& sm, uint64_t gid, uint32_t k, uint32_t r, ActT m0, ActT m1, ActT& a0, ActT& a1) {
+    uint32_t c[4] = {r, 4u + 256u * k, (uint32_t)gid, (uint32_t)(gid >> 32)};
+    sbr_philox(c, (uint32_t)sm.seed, (uint32_t)(sm.seed >> 32));
+    const double u1 = sbr_u53(c[0], c[1]), u2 = sbr_u53(c[2], c[3]);
+    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;
+    double sn, cs;
+    sincos(ang, &sn, &cs);
+    const bool plain = sm.keep_nominal != 0 && k == 0;     // candidate 0 is the nominal tape itself: v = nominal, not nominal + 0
+    const double v0 = plain ? (double)m0 : (double)m0 + (double)sm.sigma[0] * (rad * cs);
+    const double v1 = plain ? (double)m1 : (double)m1 + (double)sm.sigma[1] * (rad * sn);
+    const ActT lo0 = (ActT)sm.lo[0], hi0 = (ActT)sm.hi[0], lo1 = (ActT)sm.lo[1], hi1 = (ActT)sm.hi[1];
+    a0 = (ActT)v0; a1 = (ActT)v1;
+    a0 = a0 < lo0 ? lo0 : (a0 > hi0 ? hi0 : a0);           // a NaN passes both comparisons and stays
+    a1 = a1 < lo1 ? lo1 : (a1 > hi1 ? hi1 : a1);
+}

@@ -38,3 +38,9 @@ class SbrEnv2Vec(SbrOSVec):
 
     def lookahead(self, *a, **k):
         raise NotImplementedError("the read-only lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
+    def lookahead_sampled(self, *a, **k):
+        raise NotImplementedError("the sampled lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
+    def mppi_update(self, *a, **k):
+        raise NotImplementedError("the MPPI tape update belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")

@@ -115,6 +115,17 @@ class ShardedSbrOS:
         (columns start .. stop - 1 of the global ones)."""
         return self.env.lookahead(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards, return_best=return_best)
 
+    def lookahead_sampled(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
+                          return_actions=False):
+        """SbrOSVec.lookahead_sampled for this rank's block: `nominal` [R, n_local, 2] is the rank's own slice of the nominal
+        tape.  The candidates are keyed by the global env id, so the results do not depend on the world size."""
+        return self.env.lookahead_sampled(nominal, fanout, sampler, n_steps=n_steps, hold=hold, return_rewards=return_rewards,
+                                          return_best=return_best, return_actions=return_actions)
+
+    def mppi_update(self, nominal, returns, sampler, temperature, shift=0, out=None, return_weights=False):
+        """SbrOSVec.mppi_update for this rank's block (`nominal`, `returns` and `out` are the rank's own slices)."""
+        return self.env.mppi_update(nominal, returns, sampler, temperature, shift=shift, out=out, return_weights=return_weights)
+
     def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
                        return_rewards=False):
         """SbrOSVec.rollout_policy for this rank's block.  `policy` is the WHOLE population on every rank: an env picks its

@@ -281,6 +281,55 @@ class SbrOSVec:
                                                    _ptr(bi), _ptr(br), self._stream()), self._h)
         return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ()))
 
+    def lookahead_sampled(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
+                          return_actions=False):
+        """lookahead over SAMPLED tapes, no candidate tensor (sbr_lookahead_sampled): `nominal` is one tape [R, N, 2]; candidate k
+        of an env is that tape plus the Gaussian perturbation `sampler` (a planner.TapeSampler) draws for (seed, global env id,
+        k, row), clamped - drawn in the lane that integrates it.  Everything else is lookahead's, and so are the results and
+        their order: returns [N, K], then the per-call rewards [n_steps, N, K] and best_index, best_return [N] if asked for; with
+        return_actions=True then the candidates exactly as they were integrated [R, N, K, 2] (the rows this launch uses; fed
+        to lookahead they give the same bits)."""
+        hold, fanout = int(hold), int(fanout)
+        a, rows, n_steps = self._tape(nominal, self._ashape, n_steps, hold)
+        sm = sampler.c_struct(self.cfg)
+        n, dev = self.num_envs, self.device
+        ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
+        rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
+        bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
+        br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
+        acts = torch.empty((-(-n_steps // hold), n, fanout, 2), dtype=self.action_dtype, device=dev) if return_actions else None
+        _capi.check(self.lib.sbr_lookahead_sampled(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm), _ptr(ret),
+                                                   _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts), self._stream()), self._h)
+        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ())
+                           + ((acts,) if return_actions else ()))
+
+    def mppi_update(self, nominal, returns, sampler, temperature, shift=0, out=None, return_weights=False):
+        """The MPPI update of a nominal tape (sbr_mppi_update): `nominal` [R, N, 2] and `sampler` as given to lookahead_sampled,
+        `returns` [N, K] as it wrote them.  Per env the candidates - drawn again, not read - are averaged under the weights
+        softmax(returns / temperature) (a NaN return weighs 0; an env without a finite maximum keeps its tape); the result,
+        advanced by `shift` rows with its last row repeated, is written to `out` [R, N, 2] (a new tensor by default; out=nominal
+        updates in place).  Returns out, with return_weights=True also the normalised weights [N, K] float64."""
+        shape = tuple(getattr(nominal, "shape", ()))
+        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == self._ashape):
+            raise ValueError("nominal must have shape [R,N,2] with R >= 1")
+        a = self._as_actions(nominal, shape)
+        if out is not None and a is not nominal and out is nominal:
+            raise ValueError("out=nominal needs nominal as a contiguous tensor of the env's action dtype on its device")
+        if not (isinstance(returns, torch.Tensor) and returns.dtype == torch.float64 and returns.device == self.device
+                and returns.is_contiguous() and returns.dim() == 2 and returns.shape[0] == self.num_envs and returns.shape[1] >= 1):
+            raise ValueError("returns must be a contiguous float64 tensor of shape [N,K] on %s" % self.device)
+        if out is None:
+            out = torch.empty_like(a)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == self.action_dtype and out.device == self.device
+                  and out.is_contiguous() and tuple(out.shape) == shape):
+            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (self.action_dtype, shape, self.device))
+        sm = sampler.c_struct(self.cfg)
+        w = torch.empty_like(returns) if return_weights else None
+        self._keep_a = (a, returns)
+        _capi.check(self.lib.sbr_mppi_update(self._h, shape[0], int(returns.shape[1]), _ptr(a), C.byref(sm), _ptr(returns),
+                                             float(temperature), int(shift), _ptr(out), _ptr(w), self._stream()), self._h)
+        return (out, w) if return_weights else out
+
     def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
                        return_rewards=False):
         """Fused step() calls per env in CLOSED loop under `policy` (an MlpPolicy, or a population from MlpPolicy.stack), one

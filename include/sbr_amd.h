@@ -329,6 +329,61 @@ int sbr_rollout_actions(sbr_env* env, int32_t n_steps, int32_t hold, const void*
 int sbr_lookahead_actions(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions, double* returns,
                           double* rewards_out, int32_t* best_index, double* best_return, void* stream);
 
+/* SAMPLED lookahead and the MPPI tape update: a sampling planner's whole iteration (perturb the nominal tape K times, score,
+ * weight, average, advance) without a candidate tensor anywhere.  A candidate is a pure function of (seed, GLOBAL env id,
+ * candidate, row), so the branch that integrates it draws it in its own lane and the update draws it again.
+ *
+ * THE SAMPLE a(g, k, r, c): env with GLOBAL id g, candidate k, launch-relative row r, component c (0 = u_DO, 1 = u_EC).
+ *   (z_0, z_1)  one Box-Muller pair of Philox4x32-10, built as sbr_rollout_policy builds its noise pair: key = seed,
+ *               counter = (r, 4 + 256*k, g_lo, g_hi) - stream 4 (0 - 3 are taken), k in the upper 24 bits of the stream word
+ *   v = (double)nominal[r][i][c] + (double)sigma[c] * z_c          one multiply, one add, not fused
+ *   a = (ActT)v, then a < lo ? lo : (a > hi ? hi : a) with lo[c], hi[c] cast to ActT (a NaN nominal stays NaN)
+ *   keep_nominal = 1 and k = 0: v = nominal[r][i][c], no noise - candidate 0 is the (clamped) nominal tape itself.
+ * ActT is the handle's action type (float32, or float64 with cfg.act_f64 = 1).  The sample depends on nothing else: not on
+ * N, fanout, hold, the handle's state or the shard. */
+typedef struct sbr_sampler {
+    float sigma[2];        /* std of the perturbation of (u_DO, u_EC); >= 0, finite */
+    float lo[2], hi[2];    /* candidates are clamped into [lo, hi]; finite, lo <= hi */
+    uint64_t seed;
+    int32_t keep_nominal;  /* 1: candidate 0 of every env is the nominal tape itself (clamped, no noise) */
+    int32_t reserved_;     /* MUST be 0 */
+} sbr_sampler;             /* 40 bytes */
+
+/* sbr_lookahead_actions over SAMPLED tapes: branch j = i*fanout + k plays the tape a(g, k, ., .) of env i (global id g) from
+ * env i's current state.
+ *   nominal     [ceil(n_steps / hold)][N][2] ActT, DEVICE pointer: the tape the candidates are drawn around
+ *   actions_out [ceil(n_steps / hold)][N*fanout][2] ActT or NULL: the candidates exactly as they were integrated
+ *   returns, rewards_out, best_index, best_return: the layouts, the rule of the winner and the requirement (returns with
+ *               best_*) of sbr_lookahead_actions
+ * In every other respect the call IS sbr_lookahead_actions: rows held `hold` calls and launch-relative, a done branch skips its
+ * remaining calls with reward 0, no terminal phases, the end-of-cycle reward of reward_kind 2 inside the done call, the
+ * register budget by N*fanout, NOTHING of the handle written, nothing allocated, n_steps = 0 writes zeros and reads nothing.
+ * Fed this call's actions_out, sbr_lookahead_actions returns the same bits in returns, rewards_out and best_*.
+ * SBR_ERR_INVALID, before anything is touched: NULL env or sampler; a negative or non-finite sigma; a non-finite lo or hi, or
+ * lo > hi; reserved_ != 0; fanout < 1 or > 2^24; N*fanout >= 2^31; n_steps < 0; hold < 1; nominal NULL with n_steps > 0;
+ * best_index or best_return given while returns is NULL. */
+int sbr_lookahead_sampled(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
+                          const sbr_sampler* sampler, double* returns, double* rewards_out, int32_t* best_index,
+                          double* best_return, void* actions_out, void* stream);
+
+/* the MPPI update of the nominal tape from the returns of sbr_lookahead_sampled (same nominal, sampler, fanout and rows).
+ * Per env, over its `fanout` returns: key_k = returns[k] with NaN replaced by -inf; m = max key; if m is finite
+ * w_k = exp((key_k - m) * inv), inv = 1.0 / temperature formed once on the host (a key of -inf gives w_k = 0), S = sum w_k and
+ *   u[r][c] = (ActT)(sum_k w_k * (double)a(g, k, r, c) / S)      a: the sample above, drawn again - a convex combination
+ * of the candidates, so inside [lo, hi].  If m is not finite (every return NaN or -inf, or one +inf) u[r] = nominal[r] bit for
+ * bit and the weights are 0.  Output row r is u[min(r + shift, rows - 1)]: shift = 1 advances the tape by one decision and
+ * repeats the last row (receding horizon).  The sums run in an order fixed by k alone, so an env's output depends on its
+ * global id, its returns and the arguments - not on N, its position in the handle or the world size.
+ *   nominal_out [rows][N][2] ActT, DEVICE pointer; MAY be the same pointer as nominal (any shift), not otherwise overlapping
+ *   weights_out [N*fanout] float64 or NULL: w_k / S
+ * Nothing of the handle is read but its size, id offset and action type; nothing is allocated (graph-capturable).
+ * SBR_ERR_INVALID, before anything is touched: NULL env, sampler, nominal, returns or nominal_out; the sampler refusals
+ * above; fanout < 1 or > 2^24; N*fanout >= 2^31; rows < 1; temperature not > 0, or temperature or 1/temperature not finite;
+ * shift < 0. */
+int sbr_mppi_update(sbr_env* env, int32_t rows, int32_t fanout, const void* nominal, const sbr_sampler* sampler,
+                    const double* returns, double temperature, int32_t shift, void* nominal_out, double* weights_out,
+                    void* stream);
+
 /* fused rollout in CLOSED loop under the caller's policy: n_steps fused step() calls per env in ONE kernel, the action of a
  * decision call being a small MLP applied to the env's float32 observation, evaluated on the device next to the plant
  * (policy evaluation, evolution strategies and populations, collectors).
