@@ -443,6 +443,11 @@ SBR_DEV void sbr_rk4(const SbrPar& p, double (&x)[SBR_NX], double h, int n, doub
 //   the done call only (Kla held) it was accurate, 0.0036 of the gate, and took 231 -> 204 us off that call = 0.06 us per call of
 //   an episode: measured, not adopted.  profiles/r06_notes.md section 2; scripts/analysis/knee_study.py idle.)
 // Returns the plan it ran with: step count (<= 64) + SBR_PLAN_SLAVED if dissolved oxygen was held (sbr_amd.h, SBR_C_PLAN).
+//   What pins which count (tests/plan_cases.py, tests/test_plan_branches_gpu.py): the END STATE of a call is compared with the CPU
+//   oracle's, in the DOSE and in the plain build and through every kernel that inlines this function, at 1, 2 and 4 steps by z, 2 and
+//   4 by the n_s floor, slaved at 2 and 4 (plans 130, 132), at knee counts from 5 to 63 (general h = span sbr_rcp(n)) and at 64 where
+//   q lies in [63, 64); the idle phase's general span (sbr_b5a_span) at 1 .. 27 steps.  By COUNT only: the domain guard (the state is
+//   garbage by premise) and the cap of 64 with q >= 64, beyond what 64 steps can integrate (lam(0) h > 2.5; the state may overflow).
 struct SbrB5C { double a21, a31, a42, a51, a54, a61, a62, a63, a65, b1, b3, b4; };
 template <bool DOSE>
 SBR_DEV int sbr_b5a(const SbrPar& p, double (&x)[SBR_NX], double span, double kla, double Q) {

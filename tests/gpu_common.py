@@ -1,5 +1,5 @@
-"""What the GPU tests of the fused entry points (tests/test_tape_rollout_gpu.py, tests/test_policy_rollout_gpu.py,
-tests/test_lookahead_gpu.py) share: the package behind their `G` fixtures, the seeded inputs, handles behind a non-default config
+"""What the GPU tests share (the fused entry points: tests/test_tape_rollout_gpu.py, tests/test_policy_rollout_gpu.py,
+tests/test_lookahead_gpu.py; the plan rule: tests/test_gpu_parity.py, tests/test_plan_branches_gpu.py): the package behind their `G` fixtures, the seeded inputs, handles behind a non-default config
 and the check that no env left the model's domain.  A plain module: pytest does not rewrite its asserts, so each carries its
 message."""
 import os
@@ -55,3 +55,19 @@ def no_flags(status):
     """`status`: the C_STATUS row of a handle, [N] float64 on the device."""
     st = to_np(status).astype(np.int64)
     assert np.count_nonzero(st & FLAGS) == 0, "%d envs flagged" % np.count_nonzero(st & FLAGS)
+
+
+def plans_agree(ctrl, ora, where=None, pick=None):
+    """the plan of cfg.scheme = 1 - Butcher-5 step count and the slaved bit of the env's last interval - as the
+    DEVICE reports it (SBR_C_PLAN, from the meta row) equals the oracle's for the same call.  A decision that flipped (a rounded
+    double on the other side of 0.3 / 1.0 / 1e-9) would show as a ~1e-2-gate mismatch otherwise indistinguishable from a wrong kernel."""
+    from gym_sbr2_amd import _capi
+    dev = np.asarray(ctrl[_capi.C_PLAN]).astype(np.int64)
+    if pick is not None:
+        dev = dev[pick]
+    ref = ora.envs["scheme_plan"].astype(np.int64) & 0xff
+    if where is not None:
+        dev, ref = dev[where], ref[where]
+    bad = np.nonzero(dev != ref)[0]
+    assert bad.size == 0, ("plan flipped on %d envs; first: device %d, oracle %d" % (bad.size, dev[bad[0]], ref[bad[0]]))
+    return dev

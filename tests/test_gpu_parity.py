@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 from conftest import BENCH_SCENARIOS, EPISODES, HELDOUT_EPISODES, SCENARIO_EPISODES, gate, golden, obs_tolerance, valid_calls
+from gpu_common import plans_agree as _plans_agree
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -34,22 +35,6 @@ def G():
 
 def _np(t):
     return t.detach().cpu().numpy()
-
-
-def _plans_agree(ctrl, ora, where=None, pick=None):
-    """the plan of cfg.scheme = 1 - Butcher-5 step count and the slaved bit of the env's last interval - as the
-    DEVICE reports it (SBR_C_PLAN, from the meta row) equals the oracle's for the same call.  A decision that flipped (a rounded
-    double on the other side of 0.3 / 1.0 / 1e-9) would show as a ~1e-2-gate mismatch otherwise indistinguishable from a wrong kernel."""
-    from gym_sbr2_amd import _capi
-    dev = np.asarray(ctrl[_capi.C_PLAN]).astype(np.int64)
-    if pick is not None:
-        dev = dev[pick]
-    ref = ora.envs["scheme_plan"].astype(np.int64) & 0xff
-    if where is not None:
-        dev, ref = dev[where], ref[where]
-    bad = np.nonzero(dev != ref)[0]
-    assert bad.size == 0, ("plan flipped on %d envs; first: device %d, oracle %d" % (bad.size, dev[bad[0]], ref[bad[0]]))
-    return dev
 
 
 def test_native_library_is_loaded_and_fails_loudly_on_bad_config(G):
