@@ -87,6 +87,10 @@ SYMBOLS = {
     "sbr_rollout_actions": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_actions": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_sampled": (C.c_int, [_VP, _I32, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_lookahead_actions_end": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_lookahead_sampled_end": (C.c_int, [_VP, _I32, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                            _VP]),
+    "sbr_branch_best": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP]),
     "sbr_mppi_update": (C.c_int, [_VP, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, C.c_double, _I32, _VP, _VP, _VP]),
     "sbr_policy_param_count": (_I64, [_I32, _I32]),
     "sbr_rollout_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP]),

@@ -13,6 +13,8 @@
 //              the handle written; then the per-env winner of the K returns, one wavefront per env
 //   k_lookahead_sampled, k_mppi_update   the fan-out over tapes each branch SAMPLES around a nominal tape in its own lane, and the
 //              softmax-weighted update of that tape with the candidates drawn again: no candidate tensor anywhere
+//   k_lookahead_tape_end, k_lookahead_sampled_end   the two fan-outs reporting where each branch ended - observation, state, done
+//              flag - for a terminal value on top of its return
 //   k_cycle_reset, k_cycle   the per-cycle env SBR-v2: one launch = one whole 12 h cycle (528 control intervals)
 //   k_export, k_import, k_m1_explicit   public <-> internal controller layout; implicit So[-1] / Sno[-1] made explicit
 //   k_stats    wavefront (DPP) reductions of a per-env vector -> {sum,min,max,count}
@@ -1108,6 +1110,161 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_sampled(SbrPar p
     if (returns) (returns + j0)[l] = acc;
 }
 
+// Where a branch ENDED (sbr_lookahead_actions_end / sbr_lookahead_sampled_end), for a terminal value on top of its return: stored
+// once per launch and branch, behind the loop.  Each output is optional (wave-uniform tests).  A branch that is not done: the
+// rows k_step forms for a call that does not end the episode - sbr_write_obs / sbr_write_state of the plant, the last interval's
+// start values (x6) and the running time c.t, which is sbr_finish_step's t_obs for such a call - the observation as
+// k_rollout_policy writes it back on exit.  A done branch (on entry or during the launch): zeros; its plant stopped at the done
+// call without the terminal phases, a state no other entry point reports.  float32 whatever cfg.out_f64 says, like the policy
+// kernel's observation.  Plain per-lane stores, 72 and 60 bytes per lane at a lane stride of 72 and 60: the wave's rows are
+// contiguous, so every byte of the lines it touches is written.  The 18 + 15 stores of the source are adjacent, and the backend
+// merges them into 16-byte ones (5 per obs_end row, 4 per state_end row) - once per launch, not per call,
+// where k_step transposes its rows through LDS on every call.
+SBR_DEV void sbr_store_branch_end(int64_t j0, uint32_t l, bool done, double t, const double (&x)[SBR_NX], const SbrX6Reg& x6,
+                                  float* __restrict__ obs_end, float* __restrict__ state_end, uint8_t* __restrict__ done_end) {
+    if (done_end) (done_end + j0)[l] = (uint8_t)(done ? 1 : 0);
+    if (obs_end) {
+        float o[SBR_NOBS];
+#pragma unroll
+        for (int k = 0; k < SBR_NOBS; ++k) o[k] = 0.0f;
+        if (!done) {
+            double xa6[SBR_NXD];
+            x6.get(xa6);
+            sbr_write_obs<float>(o, 1, t, x, xa6, x);
+        }
+        float* mine = obs_end + j0 * SBR_NOBS + l * (uint32_t)SBR_NOBS;
+#pragma unroll
+        for (int k = 0; k < SBR_NOBS; ++k) mine[k] = o[k];
+    }
+    if (state_end) {
+        float sv[SBR_NSTATE];
+#pragma unroll
+        for (int k = 0; k < SBR_NSTATE; ++k) sv[k] = 0.0f;
+        if (!done) sbr_write_state<float>(sv, 1, t, x);
+        float* mine = state_end + j0 * SBR_NSTATE + l * (uint32_t)SBR_NSTATE;
+#pragma unroll
+        for (int k = 0; k < SBR_NSTATE; ++k) mine[k] = sv[k];
+    }
+}
+
+// k_lookahead_tape that also reports where each branch ended.  A kernel of its own and not a parameter of k_lookahead_tape: the
+// tests address that kernel by its mangled name and pin its registers and its store count, and a caller that wants no end state
+// pays nothing for this one.  The loop is REPEATED, not shared: moving the parent's loop into a device function would be a
+// change to the parent, and its instruction text is to stay what it is.  Same arithmetic on the same values in the same order,
+// so returns and rewards_out are the parent's bits.  n_steps >= 1 (the host refuses 0: the handle already holds that state).
+template <typename ActT, bool OCI, int SCH, int WAVES>
+__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_tape_end(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
+                                                                 uint32_t n_branch, const ActT* __restrict__ actions,
+                                                                 double* __restrict__ returns, double* __restrict__ rewards_out,
+                                                                 float* __restrict__ obs_end, float* __restrict__ state_end,
+                                                                 uint8_t* __restrict__ done_end) {
+    const uint32_t l = threadIdx.x;
+    const uint32_t j0u = blockIdx.x * (uint32_t)SBR_BLOCK;   // n_branch < 2^31 (checked by the host): 32 bits hold every branch index
+    if (j0u + l >= n_branch) return;
+    const int64_t j0 = (int64_t)j0u;
+    const uint32_t e0u = j0u / fanout;                       // the (e0, el) addressing of the env's rows: see k_lookahead_tape
+    const uint32_t el = ((j0u + l) / fanout - e0u) & 511u;
+    const int64_t e0 = (int64_t)e0u;
+    double x[SBR_NX], xa6[SBR_NXD];
+    SbrX6Reg x6;
+    SbrRewardParts rp;
+    load_x(b, e0, el, x);
+    SbrRecord rec;
+    load_record<OCI>(p, b, e0, el, x[8], x[9], rec);
+    SbrCtl& c = rec.c;
+    bool done = rec.meta.done;
+    const ActT* row = actions + j0 * 2;
+    ActT a0, a1;
+    tape_load(row, l, a0, a1);
+    int32_t left = hold;
+    double acc = 0.0;
+    for (int32_t s = 0; s < n_steps; ++s) {
+        ActT n0 = a0, n1 = a1;
+        if (--left == 0 && s + 1 < n_steps) {
+            row += (int64_t)n_branch * 2; left = hold;
+            tape_load(row, l, n0, n1);
+        }
+        double r = 0.0;
+        if (!done) {
+            double t_obs;
+            bool dn;
+            sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
+            x6.get(xa6);
+            SbrHistReg hs{rec.hist};
+            r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, rec.qw, rec.ksum, rp);
+            acc += r;
+            if (dn) done = true;
+        }
+        if (rewards_out) (rewards_out + ((int64_t)s * n_branch + j0))[l] = r;
+        a0 = n0; a1 = n1;
+    }
+    if (returns) (returns + j0)[l] = acc;
+    sbr_store_branch_end(j0, l, done, c.t, x, x6, obs_end, state_end, done_end);
+}
+
+// k_lookahead_sampled that also reports where each branch ended: its loop repeated, for the reasons given at
+// k_lookahead_tape_end, with sbr_tape_sample at its one site.
+template <typename ActT, bool OCI, int SCH, int WAVES>
+__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_sampled_end(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
+                                                                    uint32_t n_branch, const ActT* __restrict__ nominal, sbr_sampler sm,
+                                                                    double* __restrict__ returns, double* __restrict__ rewards_out,
+                                                                    ActT* __restrict__ actions_out, float* __restrict__ obs_end,
+                                                                    float* __restrict__ state_end, uint8_t* __restrict__ done_end) {
+    const uint32_t l = threadIdx.x;
+    const uint32_t j0u = blockIdx.x * (uint32_t)SBR_BLOCK;   // n_branch < 2^31 (checked by the host): 32 bits hold every branch index
+    if (j0u + l >= n_branch) return;
+    const int64_t j0 = (int64_t)j0u;
+    const uint32_t e0u = j0u / fanout;                       // the (e0, el) addressing of the env's rows: see k_lookahead_tape
+    const uint32_t eu = (j0u + l) / fanout;
+    const uint32_t el = (eu - e0u) & 511u;
+    const uint32_t k = j0u + l - eu * fanout;                // the lane's candidate
+    const int64_t e0 = (int64_t)e0u;
+    const uint64_t gid = (uint64_t)(b.first_env_id + e0) + el;
+    double x[SBR_NX], xa6[SBR_NXD];
+    SbrX6Reg x6;
+    SbrRewardParts rp;
+    load_x(b, e0, el, x);
+    SbrRecord rec;
+    load_record<OCI>(p, b, e0, el, x[8], x[9], rec);
+    SbrCtl& c = rec.c;
+    bool done = rec.meta.done;
+    typedef typename SbrAct2<ActT>::type Act2;
+    const ActT* row = nominal + e0 * 2;
+    ActT* out = actions_out ? actions_out + j0 * 2 : nullptr;
+    ActT m0, m1, a0 = 0, a1 = 0;
+    tape_load(row, el, m0, m1);
+    uint32_t r = 0;                                // the launch-relative row that comes into force next
+    bool draw = true;
+    int32_t left = hold;
+    double acc = 0.0;
+    for (int32_t s = 0; s < n_steps; ++s) {
+        if (draw) {
+            sbr_tape_sample<ActT>(sm, gid, k, r, m0, m1, a0, a1);
+            if (out) { Act2 v; v.x = a0; v.y = a1; *reinterpret_cast<Act2*>(out + 2 * l) = v; out += (int64_t)n_branch * 2; }
+            ++r;
+        }
+        draw = --left == 0 && s + 1 < n_steps;
+        if (draw) {
+            row += b.n * 2; left = hold;
+            tape_load(row, el, m0, m1);
+        }
+        double rw = 0.0;
+        if (!done) {
+            double t_obs;
+            bool dn;
+            sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
+            x6.get(xa6);
+            SbrHistReg hs{rec.hist};
+            rw = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, rec.qw, rec.ksum, rp);
+            acc += rw;
+            if (dn) done = true;
+        }
+        if (rewards_out) (rewards_out + ((int64_t)s * n_branch + j0))[l] = rw;
+    }
+    if (returns) (returns + j0)[l] = acc;
+    sbr_store_branch_end(j0, l, done, c.t, x, x6, obs_end, state_end, done_end);
+}
+
 // The MPPI update of the nominal tape (sbr_mppi_update): one wavefront per env, four per workgroup, the shape of k_branch_best.
 // Lanes stride over the candidates; the maximum and the sums are closed by a 64-lane xor butterfly.  A lane adds its candidates
 // in ascending k and the butterfly adds pairs (commutative, so every lane ends with the same bits): the order of every sum is
@@ -2019,9 +2176,10 @@ int sbr_rollout_actions(sbr_env* e, int32_t n_steps, int32_t hold, const void* a
     });
 }
 
-int sbr_lookahead_actions(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions, double* returns,
-                          double* rewards_out, int32_t* best_index, double* best_return, void* stream) {
-    // every check is evaluated, the LAST failing one is reported - all of them before anything is touched
+// What sbr_lookahead_actions and sbr_lookahead_actions_end have to say about the arguments they share; empty if they are valid.
+// Every check is evaluated, the LAST failing one is reported - all of them before anything is touched.
+static std::string lookahead_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions,
+                                   const double* returns, const int32_t* best_index, const double* best_return) {
     std::string bad;
     if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
     if (!actions && n_steps > 0) bad = "NULL actions with n_steps > 0";
@@ -2030,6 +2188,24 @@ int sbr_lookahead_actions(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fan
     if (hold < 1) bad = "hold must be >= 1";
     if (n_steps < 0) bad = "n_steps must be >= 0";
     if (!e) bad = "NULL env";
+    return bad;
+}
+// What the two _end entry points add to their parents' refusals; empty if the arguments are valid.
+static std::string end_error(int32_t n_steps, const void* obs_end, const void* state_end, const void* done_end) {
+    if (n_steps == 0) return "n_steps = 0 has no end state to report that the handle does not already hold";
+    if (!obs_end && !state_end && !done_end) return "obs_end, state_end and done_end are all NULL: call the entry point without _end";
+    return "";
+}
+// k_branch_best behind a lookahead kernel on the same stream, or on its own (sbr_branch_best): one wavefront per env
+static void launch_branch_best(const sbr_env* e, int32_t fanout, const double* values, int32_t* best_index, double* best_value,
+                               void* stream) {
+    hipLaunchKernelGGL(k_branch_best, dim3((unsigned)((e->n + SBR_BLOCK / 64 - 1) / (SBR_BLOCK / 64))), dim3(SBR_BLOCK), 0,
+                       (hipStream_t)stream, values, e->n, (uint32_t)fanout, best_index, best_value);
+}
+
+int sbr_lookahead_actions(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions, double* returns,
+                          double* rewards_out, int32_t* best_index, double* best_return, void* stream) {
+    const std::string bad = lookahead_error(e, n_steps, hold, fanout, actions, returns, best_index, best_return);
     if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_lookahead_actions: " + bad);
     const int64_t nb = e->n * (int64_t)fanout;
     return launched(e, [&] {
@@ -2041,10 +2217,40 @@ int sbr_lookahead_actions(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fan
             hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
                                (uint32_t)nb, (const A*)actions, returns, rewards_out);
         });
-        if (best_index || best_return)
-            hipLaunchKernelGGL(k_branch_best, dim3((unsigned)((e->n + SBR_BLOCK / 64 - 1) / (SBR_BLOCK / 64))), dim3(SBR_BLOCK), 0,
-                               (hipStream_t)stream, returns, e->n, (uint32_t)fanout, best_index, best_return);
+        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
+}
+
+int sbr_lookahead_actions_end(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions, double* returns,
+                              double* rewards_out, int32_t* best_index, double* best_return, float* obs_end, float* state_end,
+                              uint8_t* done_end, void* stream) {
+    std::string bad = end_error(n_steps, obs_end, state_end, done_end);
+    const std::string pb = lookahead_error(e, n_steps, hold, fanout, actions, returns, best_index, best_return);
+    if (!pb.empty()) bad = pb;
+    if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_lookahead_actions_end: " + bad);
+    const int64_t nb = e->n * (int64_t)fanout;
+    return launched(e, [&] {
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            using A = typename C::ActT;
+            // the register budget goes by the branches, as in sbr_lookahead_actions
+            const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_tape_end<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_tape_end<A, C::OCI, C::SCH, 2>;
+            hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
+                               (uint32_t)nb, (const A*)actions, returns, rewards_out, obs_end, state_end, done_end);
+        });
+        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
+    });
+}
+
+int sbr_branch_best(sbr_env* e, int32_t fanout, const double* values, int32_t* best_index, double* best_value, void* stream) {
+    std::string bad;
+    if (!best_index && !best_value) bad = "best_index and best_value are both NULL";
+    if (!values) bad = "NULL values";
+    if (fanout < 1) bad = "fanout must be >= 1";
+    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+    if (!e) bad = "NULL env";
+    if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_branch_best: " + bad);
+    return launched(e, [&] { launch_branch_best(e, fanout, values, best_index, best_value, stream); });
 }
 
 // What sbr_lookahead_sampled and sbr_mppi_update have to say about a sampler and a fan-out; empty if they are valid.
@@ -2061,11 +2267,10 @@ static std::string sampler_error(const sbr_env* e, const sbr_sampler* sm, int32_
     if (sm->reserved_ != 0) bad = "sampler.reserved_ must be 0";
     return bad;
 }
-
-int sbr_lookahead_sampled(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal, const sbr_sampler* sampler,
-                          double* returns, double* rewards_out, int32_t* best_index, double* best_return, void* actions_out,
-                          void* stream) {
-    // every check is evaluated, the LAST failing one is reported - all of them before anything is touched
+// The same for sbr_lookahead_sampled and sbr_lookahead_sampled_end: the LAST failing check is reported.
+static std::string lookahead_sampled_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
+                                           const sbr_sampler* sampler, const double* returns, const int32_t* best_index,
+                                           const double* best_return) {
     std::string bad;
     if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
     if (!nominal && n_steps > 0) bad = "NULL nominal with n_steps > 0";
@@ -2074,6 +2279,13 @@ int sbr_lookahead_sampled(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fan
     if (hold < 1) bad = "hold must be >= 1";
     if (n_steps < 0) bad = "n_steps must be >= 0";
     if (!e) bad = "NULL env";
+    return bad;
+}
+
+int sbr_lookahead_sampled(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal, const sbr_sampler* sampler,
+                          double* returns, double* rewards_out, int32_t* best_index, double* best_return, void* actions_out,
+                          void* stream) {
+    const std::string bad = lookahead_sampled_error(e, n_steps, hold, fanout, nominal, sampler, returns, best_index, best_return);
     if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_lookahead_sampled: " + bad);
     const int64_t nb = e->n * (int64_t)fanout;
     return launched(e, [&] {
@@ -2085,9 +2297,29 @@ int sbr_lookahead_sampled(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fan
             hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
                                (uint32_t)nb, (const A*)nominal, *sampler, returns, rewards_out, (A*)actions_out);
         });
-        if (best_index || best_return)
-            hipLaunchKernelGGL(k_branch_best, dim3((unsigned)((e->n + SBR_BLOCK / 64 - 1) / (SBR_BLOCK / 64))), dim3(SBR_BLOCK), 0,
-                               (hipStream_t)stream, returns, e->n, (uint32_t)fanout, best_index, best_return);
+        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
+    });
+}
+
+int sbr_lookahead_sampled_end(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
+                              const sbr_sampler* sampler, double* returns, double* rewards_out, int32_t* best_index,
+                              double* best_return, void* actions_out, float* obs_end, float* state_end, uint8_t* done_end,
+                              void* stream) {
+    std::string bad = end_error(n_steps, obs_end, state_end, done_end);
+    const std::string pb = lookahead_sampled_error(e, n_steps, hold, fanout, nominal, sampler, returns, best_index, best_return);
+    if (!pb.empty()) bad = pb;
+    if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_lookahead_sampled_end: " + bad);
+    const int64_t nb = e->n * (int64_t)fanout;
+    return launched(e, [&] {
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            using A = typename C::ActT;
+            const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_sampled_end<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_sampled_end<A, C::OCI, C::SCH, 2>;
+            hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
+                               (uint32_t)nb, (const A*)nominal, *sampler, returns, rewards_out, (A*)actions_out, obs_end, state_end,
+                               done_end);
+        });
+        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
 }
 

@@ -42,5 +42,14 @@ class SbrEnv2Vec(SbrOSVec):
     def lookahead_sampled(self, *a, **k):
         raise NotImplementedError("the sampled lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 
+    def lookahead_end(self, *a, **k):
+        raise NotImplementedError("the read-only lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
+    def lookahead_sampled_end(self, *a, **k):
+        raise NotImplementedError("the sampled lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
+    def branch_best(self, *a, **k):
+        raise NotImplementedError("the winner of a lookahead's branches belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
     def mppi_update(self, *a, **k):
         raise NotImplementedError("the MPPI tape update belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")

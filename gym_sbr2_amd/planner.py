@@ -1,7 +1,7 @@
 """Sampling planners on the fused lookahead: the sampler of candidate tapes (struct sbr_sampler) and a thin MPPI loop.
 
 Plumbing only: the candidates are drawn, scored and averaged inside libsbr_amd.so (sbr_lookahead_sampled, sbr_mppi_update);
-nothing here does arithmetic on a candidate."""
+nothing here does arithmetic on a candidate.  The one sum formed here adds the caller's terminal value to a return."""
 import ctypes as C
 
 import numpy as np
@@ -51,7 +51,13 @@ class MppiPlanner:
 
         planner = MppiPlanner(env, rows=50, fanout=64, sampler=TapeSampler((0.3, 2.0)), temperature=5.0)
         while ...: env.step(planner.plan())
+
+    A TERMINAL VALUE for what lies beyond the horizon: assign `planner.terminal_value`, a callable taking (obs_end [N, K, 18],
+    state_end [N, K, 15]), float32, and returning a tensor [N, K] - the caller's critic, plain torch code.  plan() then scores
+    with lookahead_sampled_end and weighs the candidates by return + where(done_end, 0, terminal_value(...)); with
+    return_returns=True it returns those adjusted returns.  None (the default): the planner scores by the returns alone.
     """
+    terminal_value = None
 
     def __init__(self, env, rows, fanout, sampler, temperature, hold=1):
         import torch
@@ -70,7 +76,12 @@ class MppiPlanner:
         """One decision: the action [N, 2] to give to step() (a view that stays valid until the plan after next); with
         return_returns=True also the candidates' returns [N, K]."""
         sm = self.sampler.with_seed(self.sampler.seed + self.decision)
-        ret = self.env.lookahead_sampled(self.nominal, self.fanout, sm, hold=self.hold)
+        if self.terminal_value is None:
+            ret = self.env.lookahead_sampled(self.nominal, self.fanout, sm, hold=self.hold)
+        else:
+            ret, obs_end, state_end, done_end = self.env.lookahead_sampled_end(self.nominal, self.fanout, sm, hold=self.hold)
+            v = self.terminal_value(obs_end, state_end).double()
+            ret = (ret + v.masked_fill(done_end, 0.0)).contiguous()
         self._cur ^= 1
         buf = self._bufs[self._cur]
         self.env.mppi_update(self.nominal, ret, sm, self.temperature, out=buf[:self.rows])

@@ -122,6 +122,20 @@ class ShardedSbrOS:
         return self.env.lookahead_sampled(nominal, fanout, sampler, n_steps=n_steps, hold=hold, return_rewards=return_rewards,
                                           return_best=return_best, return_actions=return_actions)
 
+    def lookahead_end(self, actions, n_steps=None, hold=1, return_rewards=False, return_best=False):
+        """SbrOSVec.lookahead_end for this rank's block (`actions` and every result are the rank's own slices)."""
+        return self.env.lookahead_end(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards, return_best=return_best)
+
+    def lookahead_sampled_end(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
+                              return_actions=False):
+        """SbrOSVec.lookahead_sampled_end for this rank's block (`nominal` and every result are the rank's own slices)."""
+        return self.env.lookahead_sampled_end(nominal, fanout, sampler, n_steps=n_steps, hold=hold, return_rewards=return_rewards,
+                                              return_best=return_best, return_actions=return_actions)
+
+    def branch_best(self, values):
+        """SbrOSVec.branch_best for this rank's block: `values` [n_local, K] is the rank's own slice."""
+        return self.env.branch_best(values)
+
     def mppi_update(self, nominal, returns, sampler, temperature, shift=0, out=None, return_weights=False):
         """SbrOSVec.mppi_update for this rank's block (`nominal`, `returns` and `out` are the rank's own slices)."""
         return self.env.mppi_update(nominal, returns, sampler, temperature, shift=shift, out=out, return_weights=return_weights)

@@ -269,6 +269,23 @@ class SbrOSVec:
         launch's rewards per candidate [N, K] float64; with return_rewards=True also the reward of every call [n_steps, N, K]
         float64 (0 for a call a candidate skipped because its episode had ended); with return_best=True also best_index [N]
         int32 and best_return [N] float64: per env the largest return, NaN counting as -inf, ties to the lowest index."""
+        return self._lookahead(actions, n_steps, hold, return_rewards, return_best, False)
+
+    def lookahead_end(self, actions, n_steps=None, hold=1, return_rewards=False, return_best=False):
+        """lookahead that also reports where every branch ended (sbr_lookahead_actions_end), for a terminal value on top of the
+        returns: lookahead's results - the same bits - followed by obs_end [N, K, 18] float32, state_end [N, K, 15] float32 and
+        done_end [N, K] bool.  For a candidate whose episode has not ended the two rows are what step() returns for the
+        candidate's last call (float32 whatever the handle's output dtype); for one that is done (done_end) they are zeros.
+        At least one call: n_steps = 0 is refused."""
+        return self._lookahead(actions, n_steps, hold, return_rewards, return_best, True)
+
+    def _end_outputs(self, fanout):
+        n, dev = self.num_envs, self.device
+        return (torch.empty((n, fanout, _capi.NOBS), dtype=torch.float32, device=dev),
+                torch.empty((n, fanout, _capi.NSTATE), dtype=torch.float32, device=dev),
+                torch.empty((n, fanout), dtype=torch.bool, device=dev))        # one byte per branch, written as 0 / 1
+
+    def _lookahead(self, actions, n_steps, hold, return_rewards, return_best, end):
         hold = int(hold)
         a, rows, n_steps = self._tape(actions, (self.num_envs, None, 2), n_steps, hold)
         fanout = int(a.shape[2])
@@ -277,9 +294,15 @@ class SbrOSVec:
         rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
         bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
         br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
-        _capi.check(self.lib.sbr_lookahead_actions(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, _ptr(ret), _ptr(rew),
-                                                   _ptr(bi), _ptr(br), self._stream()), self._h)
-        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ()))
+        ends = self._end_outputs(fanout) if end else ()
+        if end:
+            _capi.check(self.lib.sbr_lookahead_actions_end(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, _ptr(ret),
+                                                           _ptr(rew), _ptr(bi), _ptr(br), *[_ptr(t) for t in ends], self._stream()),
+                        self._h)
+        else:
+            _capi.check(self.lib.sbr_lookahead_actions(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, _ptr(ret), _ptr(rew),
+                                                       _ptr(bi), _ptr(br), self._stream()), self._h)
+        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ()) + ends)
 
     def lookahead_sampled(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
                           return_actions=False):
@@ -289,6 +312,15 @@ class SbrOSVec:
         their order: returns [N, K], then the per-call rewards [n_steps, N, K] and best_index, best_return [N] if asked for; with
         return_actions=True then the candidates exactly as they were integrated [R, N, K, 2] (the rows this launch uses; fed
         to lookahead they give the same bits)."""
+        return self._lookahead_sampled(nominal, fanout, sampler, n_steps, hold, return_rewards, return_best, return_actions, False)
+
+    def lookahead_sampled_end(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
+                              return_actions=False):
+        """lookahead_sampled that also reports where every branch ended (sbr_lookahead_sampled_end): lookahead_sampled's results -
+        the same bits - followed by obs_end [N, K, 18], state_end [N, K, 15] and done_end [N, K] as lookahead_end gives them."""
+        return self._lookahead_sampled(nominal, fanout, sampler, n_steps, hold, return_rewards, return_best, return_actions, True)
+
+    def _lookahead_sampled(self, nominal, fanout, sampler, n_steps, hold, return_rewards, return_best, return_actions, end):
         hold, fanout = int(hold), int(fanout)
         a, rows, n_steps = self._tape(nominal, self._ashape, n_steps, hold)
         sm = sampler.c_struct(self.cfg)
@@ -298,10 +330,30 @@ class SbrOSVec:
         bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
         br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
         acts = torch.empty((-(-n_steps // hold), n, fanout, 2), dtype=self.action_dtype, device=dev) if return_actions else None
-        _capi.check(self.lib.sbr_lookahead_sampled(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm), _ptr(ret),
-                                                   _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts), self._stream()), self._h)
+        ends = self._end_outputs(fanout) if end else ()
+        if end:
+            _capi.check(self.lib.sbr_lookahead_sampled_end(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm),
+                                                           _ptr(ret), _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts),
+                                                           *[_ptr(t) for t in ends], self._stream()), self._h)
+        else:
+            _capi.check(self.lib.sbr_lookahead_sampled(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm), _ptr(ret),
+                                                       _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts), self._stream()), self._h)
         return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ())
-                           + ((acts,) if return_actions else ()))
+                           + ((acts,) if return_actions else ()) + ends)
+
+    def branch_best(self, values):
+        """The winner among each env's K values (sbr_branch_best), under the rule of lookahead's best_*: the largest value wins,
+        NaN counts as -inf, ties go to the lowest index.  `values` is [N, K] (converted to float64 on the device if needed) -
+        for instance a lookahead's returns with a terminal value added.  Returns (index [N] int32, value [N] float64)."""
+        shape = tuple(getattr(values, "shape", ()))
+        if not (len(shape) == 2 and shape[0] == self.num_envs and shape[1] >= 1):
+            raise ValueError("values must have shape [N,K] with K >= 1")
+        v = self._dev(values, torch.float64, shape)
+        bi = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
+        bv = torch.empty((self.num_envs,), dtype=torch.float64, device=self.device)
+        self._keep_a = v
+        _capi.check(self.lib.sbr_branch_best(self._h, int(shape[1]), _ptr(v), _ptr(bi), _ptr(bv), self._stream()), self._h)
+        return bi, bv
 
     def mppi_update(self, nominal, returns, sampler, temperature, shift=0, out=None, return_weights=False):
         """The MPPI update of a nominal tape (sbr_mppi_update): `nominal` [R, N, 2] and `sampler` as given to lookahead_sampled,

@@ -366,6 +366,37 @@ int sbr_lookahead_sampled(sbr_env* env, int32_t n_steps, int32_t hold, int32_t f
                           const sbr_sampler* sampler, double* returns, double* rewards_out, int32_t* best_index,
                           double* best_return, void* actions_out, void* stream);
 
+/* WHERE EACH BRANCH ENDED: sbr_lookahead_actions / sbr_lookahead_sampled that also report the end of every branch, for a
+ * terminal value (the caller's critic on the end observation or state) added to the branch's return.  Every shared argument
+ * follows the parent's contract word for word: returns, rewards_out, best_* and actions_out hold the parent's bits, NOTHING of
+ * the handle is written, nothing is allocated (graph-capturable), the register budget goes by N*fanout.
+ *   done_end    [B] uint8 or NULL: 1 if the branch's episode had ended on entry or ended during the launch, else 0
+ *   obs_end     [B][SBR_NOBS] float32 or NULL: for a branch that is not done, the observation sbr_step returns for the branch's
+ *               last call (the row sbr_rollout_policy leaves in obs); for a done branch SBR_NOBS zeros
+ *   state_end   [B][SBR_NSTATE] float32 or NULL: likewise the state row of sbr_step; for a done branch SBR_NSTATE zeros
+ * The three are float32 whatever cfg.out_f64 says (as the observation of sbr_rollout_policy is): the float32 rows of sbr_step
+ * bit for bit, the float64 rows rounded once.  A done branch reports zeros because its plant stopped at the done call without
+ * the terminal phases - a state no other entry point reports; mask a terminal value with done_end.
+ * best_* are reduced from `returns` as they stand; for the winner of returns ADJUSTED by the caller use sbr_branch_best.
+ * SBR_ERR_INVALID, before anything is touched: every refusal of the parent; obs_end, state_end and done_end all NULL (call the
+ * parent); n_steps = 0 (there is no end state to report that the handle does not already hold). */
+int sbr_lookahead_actions_end(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions,
+                              double* returns, double* rewards_out, int32_t* best_index, double* best_return, float* obs_end,
+                              float* state_end, uint8_t* done_end, void* stream);
+int sbr_lookahead_sampled_end(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
+                              const sbr_sampler* sampler, double* returns, double* rewards_out, int32_t* best_index,
+                              double* best_return, void* actions_out, float* obs_end, float* state_end, uint8_t* done_end,
+                              void* stream);
+
+/* the winner among each env's `fanout` values, under the rule of sbr_lookahead_actions' best_*, as a call of its own - for
+ * returns the caller has adjusted (a terminal value added).
+ *   values      [N*fanout] float64, DEVICE pointer
+ *   best_index  [N] int32 or NULL, best_value [N] float64 or NULL
+ * The largest value wins; NaN compares as -inf; ties go to the lowest k; best_value is the winner's entry as it stands.
+ * Nothing of the handle is read but its size; nothing is allocated (graph-capturable).
+ * SBR_ERR_INVALID, before anything is touched: NULL env or values; both outputs NULL; fanout < 1; N*fanout >= 2^31. */
+int sbr_branch_best(sbr_env* env, int32_t fanout, const double* values, int32_t* best_index, double* best_value, void* stream);
+
 /* the MPPI update of the nominal tape from the returns of sbr_lookahead_sampled (same nominal, sampler, fanout and rows).
  * Per env, over its `fanout` returns: key_k = returns[k] with NaN replaced by -inf; m = max key; if m is finite
  * w_k = exp((key_k - m) * inv), inv = 1.0 / temperature formed once on the host (a key of -inf gives w_k = 0), S = sum w_k and
