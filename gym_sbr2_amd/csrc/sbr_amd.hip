@@ -558,7 +558,8 @@ SBR_DEV void store_rows2(OutT* __restrict__ rows_a, OutT* __restrict__ rows_b, u
         "s_load_dword %0, %1, 0x538\n s_load_dword %0, %1, 0x548\n"
 // k_step's argument segment: four pointers / sizes, the flags word (+ padding), four pointers, SbrPar, SbrBuf.  The touched
 // offsets must stay inside it (a scalar load past the segment may fault) and reach its last line.
-static constexpr size_t kStepKernargBytes = 72 + sizeof(SbrPar) + sizeof(SbrBuf);
+static constexpr size_t kStepParOffset = 72;                  // where SbrPar lies in the segment, behind the leading arguments (SbrStepLead)
+static constexpr size_t kStepKernargBytes = kStepParOffset + sizeof(SbrPar) + sizeof(SbrBuf);
 static_assert(kStepKernargBytes >= 0x548 + 4 && kStepKernargBytes <= 0x548 + 56,
               "SbrPar / SbrBuf changed size: adjust the offsets of SBR_WARM_LINES to cover k_step's argument segment");
 // In two halves, issue at wave start and wait after the wave's global loads have gone out: the scratch register stays allocated
@@ -571,6 +572,36 @@ SBR_DEV uint32_t sbr_warm_kernarg_issue() {
     return t;
 }
 SBR_DEV void sbr_warm_kernarg_wait(uint32_t t) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(t) : : "memory"); }
+
+// Constants and pointers that are needed on BOTH sides of the step loops are not kept across them.  ~60 wave-uniform doubles do not
+// fit the scalar register file next to the loops' own constants: held live (or loaded once for both control intervals, or for the
+// ordinary path and the terminal phases alike) the compiler spills them into VGPR lanes - 153 spilled dwords, 604 lane operations,
+// 251 AGPR moves of store addresses in a call's straight-line code (profiles/r12_notes.md).  The argument segment is warm in the
+// scalar cache (SBR_WARM_LINES), so whatever follows a step loop reads its constants AGAIN from there: an empty asm statement
+// hides the segment pointer's origin, and loads through it can neither be merged with the ones in front of the loop nor hoisted
+// over it.  The pointer stays in SGPRs and in the constant address space (scalar loads); it must be re-made on a wave-uniform path -
+// a pointer merged behind a divergent branch would become a per-lane value and its loads vector loads.
+// sbr_kernarg_again / sbr_par_again / SbrStepLead describe k_step's argument segment and are for k_step alone.
+typedef const __attribute__((address_space(4))) char* SbrKernargPtr;
+SBR_DEV SbrKernargPtr sbr_kernarg_again() {
+    SbrKernargPtr kp = (SbrKernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    return kp;
+}
+SBR_DEV const SbrPar& sbr_par_again() { return *(const SbrPar*)(sbr_kernarg_again() + kStepParOffset); }
+template <typename OutT, typename ActT>
+struct SbrStepLead {          // k_step's leading arguments as they lie in the segment: same order and types as its parameter list (keep in step)
+    double* bx; double* bctrl; int64_t bn; const ActT* action; uint32_t flags, pad_; OutT* obs; OutT* state; OutT* reward; uint8_t* done;
+};
+static_assert(sizeof(SbrStepLead<float, float>) == kStepParOffset && sizeof(SbrStepLead<double, double>) == kStepParOffset,
+              "k_step's leading arguments changed: SbrStepLead and kStepParOffset must follow");
+template <bool AGAIN>         // the PA of sbr_run_intervals; false (the two-waves build, which parks in LDS instead): the caller's own
+struct SbrParAgain {
+    SBR_DEV const SbrPar& again(const SbrPar& p) const {
+        if constexpr (AGAIN) return sbr_par_again();
+        else return p;
+    }
+};
 
 // The leading arguments (14 dwords) are what the first global loads need; the library is built with
 // -mllvm -amdgpu-kernarg-preload-count=16, so a wave starts with them in SGPRs and issues its loads without waiting for a
@@ -602,7 +633,8 @@ struct SbrTraceRec {
 };
 
 // WAVES = 2 (scheme 1, launches with more wavefronts than the chip has SIMDs): the register budget of two resident waves per SIMD
-// (256).  The scheme-1 step loops need 320 registers with everything the call carries across them; this build parks that - 13
+// (256).  The scheme-1 step loops need more than that with everything the call carries across them (the one-wave build: 264; 322
+// before round 12, which stopped carrying constants and addresses across); this build parks that - 13
 // controller values per interval, 7 of the call, 19 around the idle phase of the done call - in the lane's LDS slots (64 KiB per
 // workgroup, two workgroups per CU) and forms the row addresses of its stores again afterwards instead of keeping them.
 // Same arithmetic, same bits.  Measured (profiles/r05_ab_two_waves.log): 65 536 envs 12.8 against 12.2 us per call (one wave per
@@ -617,6 +649,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
     // wave-major: wave w owns park[w][slot][64], 20 slots x 512 B = 10 KiB; the region is reused for the output
     // transpose (64 float64 observation rows take 9216 B, float32 observation + state rows together 8448 B)
     constexpr bool PARK = WAVES == 2;
+    constexpr bool AGAIN = !PARK && SCH == 1;    // the one-wave scheme-1 builds read constants and pointers again behind the step loops (sbr_kernarg_again)
     constexpr int NSLOT = PARK ? SBR_NPARK_2W : SBR_NPARK;
     // the upper bounds of the parking region: static LDS is limited to 64 KiB per workgroup, and the two-waves build only pays while
     // TWO of its workgroups fit the 160 KiB of a CU - one more __shared__ word would silently halve the residency
@@ -689,10 +722,15 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
             x6.park(PK_CALL_LV0, lv[0]); x6.park(PK_CALL_LV1, lv[1]); x6.park(PK_CALL_LV2, lv[2]);
             x6.park(PK_CALL_KLA_BEFORE, kla_before); x6.park(PK_CALL_V0, v0); x6.park(PK_CALL_SI0, si0); x6.park(PK_CALL_XI0, xi0);
         }
-        sbr_run_intervals<SCH>(p, c, x, a0, a1, x6, tr);
+        sbr_run_intervals<SCH>(SbrParAgain<AGAIN>().again(p), c, x, a0, a1, x6, tr, SbrParAgain<AGAIN>());
         double kla_before_r = kla_before, v0_r = v0, si0_r = si0, xi0_r = xi0;
+        if constexpr (PARK || AGAIN) asm volatile("" : "+v"(l) : : "memory");  // the row addresses of the stores are formed again from here (not kept across the integration)
+        const SbrPar& pe = SbrParAgain<AGAIN>().again(p);
+        if constexpr (AGAIN) {                    // ... from the handle's pointers as the argument segment holds them
+            const auto& ka = *(const SbrStepLead<OutT, ActT>*)sbr_kernarg_again();
+            b.x = ka.bx; b.ctrl = ka.bctrl; b.n = ka.bn;
+        }
         if constexpr (PARK) {
-            asm volatile("" : "+v"(l) : : "memory");  // the row addresses of the stores are formed again from here (not kept across the integration)
             lv[0] = x6.unpark(PK_CALL_LV0); lv[1] = x6.unpark(PK_CALL_LV1); lv[2] = x6.unpark(PK_CALL_LV2);
             kla_before_r = x6.unpark(PK_CALL_KLA_BEFORE); v0_r = x6.unpark(PK_CALL_V0); si0_r = x6.unpark(PK_CALL_SI0);
             xi0_r = x6.unpark(PK_CALL_XI0);
@@ -701,7 +739,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         SbrHistInc hs{my[SBR_PK_W8 * 64], kla_before_r, {lv[0], lv[1], lv[2]}, 0.0, false};
         if constexpr (!PARK) x6.get(xa6);
         double ksum = OCI ? my[SBR_PK_KSUM * 64] : 0.0;
-        r = sbr_finish_step<OCI, SCH, SbrHistInc, true, SbrX6LdsT<PARK>>(p, c, hs, x, xa6, t_obs, dn, qw, ksum, rp, &x6);
+        r = sbr_finish_step<OCI, SCH, SbrHistInc, true, SbrX6LdsT<PARK>>(pe, c, hs, x, xa6, t_obs, dn, qw, ksum, rp, &x6);
         if constexpr (PARK) x6.get(xa6);              // after the terminal phases, which leave their pre-settle values in the slots
         SBR_STAMP(4, false);                  // reward (and, on the done call, the terminal phases) done
         // everything that reads the three ring entries loaded before the integration comes BEFORE the first store: the memory
@@ -746,7 +784,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
             if (n_app > 2) CTRL(R_RING0 + ring_wrap(kb + 2)) = hs.idle;
         }
         st_out(&CTRL(R_KLA_LAST), last_new); st_out(&CTRL(R_W8), w8_new);
-        if (dn && p.terminal) CTRL(R_QW) = qw;
+        if (dn && pe.terminal) CTRL(R_QW) = qw;
         const SbrMeta m = SbrMeta::unpack(my[SBR_PK_META * 64]);
         const int steps = m.steps;
         st_out(&CTRL(R_RET), my[SBR_PK_RET * 64] + r);
@@ -763,7 +801,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
             rec[SBR_TR_KLA * b.n_trace] = c.knew[c.n_new > 1 ? 1 : 0]; rec[SBR_TR_EC * b.n_trace] = c.ec_last;
             rec[SBR_TR_REWARD * b.n_trace] = r; rec[SBR_TR_DONE * b.n_trace] = dn ? 1.0 : 0.0;
             rec[SBR_TR_U_DO * b.n_trace] = c.u_do; rec[SBR_TR_U_EC * b.n_trace] = c.u_ec;
-            const double ae2 = rp.ae * p.inv_ae_max, ec2 = rp.ec * p.inv_ec_max;
+            const double ae2 = rp.ae * pe.inv_ae_max, ec2 = rp.ec * pe.inv_ec_max;
             rec[SBR_TR_R_EQI * b.n_trace] = rp.eqi2; rec[SBR_TR_R_OCI * b.n_trace] = ae2 + ec2;
             rec[SBR_TR_R_AE * b.n_trace] = ae2; rec[SBR_TR_R_EC * b.n_trace] = ec2;
             rec[SBR_TR_N_IV * b.n_trace] = (double)c.n_new; rec[SBR_TR_KLA_FIRST * b.n_trace] = c.knew[0];
@@ -774,6 +812,10 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         x6.get(xa6);
     }
     SBR_STAMP(5, false);                      // state stores issued
+    if constexpr (AGAIN) {                        // behind the join of the two branches: wave-uniform again (see sbr_kernarg_again)
+        const auto& ka = *(const SbrStepLead<OutT, ActT>*)sbr_kernarg_again();
+        obs = ka.obs; state = ka.state; reward = ka.reward; done = ka.done;
+    }
     if (reward) st_out(&(reward + i0)[l], (OutT)r);
     if (done) st_out(&(done + i0)[l], (uint8_t)(dn ? 1 : 0));
     SBR_STAMP(11, false);                     // reward / done stores issued

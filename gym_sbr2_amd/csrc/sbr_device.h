@@ -684,8 +684,11 @@ SBR_DEV int sbr_status_bits(const SbrPar& p, const double (&x)[SBR_NX]) {
 // TR: where the NO3-PID's e / ie / dcv of every interval go (trajectory export; SbrNoTrace for kernels without one).
 struct SbrNoTrace { SBR_DEV void pid(int, double, double, double) const {} };
 // SCH: cfg.scheme at compile time (a kernel instantiation per scheme: the scheme-1 kernels carry no RK4 loop for the intervals).
-template <int SCH, typename X6, typename TR>
-SBR_DEV void sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& xs6, bool aerobic, const TR& tr) {
+// PA: where the constants come from AFTER the step loop (SbrParKeep: the caller's `p`; k_step reads them again, see SbrParAgain
+// in sbr_amd.hip).  Returns the set to go on with.
+struct SbrParKeep { SBR_DEV const SbrPar& again(const SbrPar& p) const { return p; } };
+template <int SCH, typename X6, typename TR, typename PA>
+SBR_DEV const SbrPar& sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& xs6, bool aerobic, const TR& tr, const PA& pa) {
     const double t0 = c.t, t1 = t0 + p.t_delta;
     const double span = t1 - t0;
     // len(t_range) = int(span/dt): 9 or 10 with the fp rounding of (t+t_delta)-t (:1339, :1384).  Exact for every span:
@@ -752,6 +755,7 @@ SBR_DEV void sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& x
         if (__builtin_amdgcn_ballot_w64(ec != 0.0) == 0ull) sbr_rk4<0>(p, x, h, p.substeps, kla, 0.0, nold);
         else sbr_rk4<1>(p, x, h, p.substeps, kla, ec, nold);
     }
+    const SbrPar& pq = pa.again(p);
     if constexpr (X6::kPark) {
         asm volatile("" ::: "memory");
         t1r = xs6.unpark(PK_IV_T1); klar = xs6.unpark(PK_IV_KLA); ecr = xs6.unpark(PK_IV_EC); spanr = xs6.unpark(PK_IV_SPAN);
@@ -769,7 +773,8 @@ SBR_DEV void sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& x
     c.so_m2 = c.so_m1; c.so_m1 = x[8];
     c.sno_m2 = c.sno_m1; c.sno_m1 = x[9];
     c.t = t1r; c.span = spanr;
-    c.st_new |= sbr_status_bits(p, x);
+    c.st_new |= sbr_status_bits(pq, x);
+    return pq;
 }
 
 // The phase logic of SbrOS.step (:860-1010): four sequential `if`s on the running time (:860 anoxic, :896 aerobic, :931
@@ -787,8 +792,9 @@ SBR_DEV int sbr_phase(const SbrPar& p, double t) {
     // every comparison is false for a NaN: -1
     return (t >= p.T3_0 ? 1 : 0) + (t > p.T3_end ? 1 : 0) + (t > p.T4_end ? 1 : 0) - (t == t ? 0 : 1);
 }
-template <int SCH, typename X6, typename TR>
-SBR_DEV void sbr_run_intervals(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], double a0, double a1, X6& xs6, const TR& tr) {
+template <int SCH, typename X6, typename TR, typename PA = SbrParKeep>
+SBR_DEV void sbr_run_intervals(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], double a0, double a1, X6& xs6, const TR& tr,
+                               const PA& pa = PA()) {
     a0 = a0 < 0.0 ? 0.0 : (a0 > p.act_DO_max ? p.act_DO_max : a0);       // :901-906
     a1 = a1 < 0.0 ? 0.0 : (a1 > p.act_EC_max ? p.act_EC_max : a1);       // :865-870
     c.n_new = 0; c.st_new = 0; c.plans = 0;
@@ -797,12 +803,12 @@ SBR_DEV void sbr_run_intervals(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], 
     if (ph >= 0) {
         const bool aerobic = (ph & 1) != 0;
         c.u_do = aerobic ? a0 : 0.0; c.u_ec = aerobic ? 0.0 : a1;
-        sbr_interval<SCH>(p, c, x, xs6, aerobic, tr);
-        const int ph2 = sbr_phase(p, c.t);
+        const SbrPar& pq = sbr_interval<SCH>(p, c, x, xs6, aerobic, tr, pa);
+        const int ph2 = sbr_phase(pq, c.t);
         if (__builtin_expect(ph2 > ph, 0)) {
             const bool aerobic2 = (ph2 & 1) != 0;
             c.u_do = aerobic2 ? a0 : 0.0; c.u_ec = aerobic2 ? 0.0 : a1;
-            sbr_interval<SCH>(p, c, x, xs6, aerobic2, tr);
+            (void)sbr_interval<SCH>(pq, c, x, xs6, aerobic2, tr, pa);
         }
     }
 }
