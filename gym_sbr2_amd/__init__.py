@@ -41,7 +41,7 @@ def __getattr__(name):          # torch is imported only when the env classes ar
     if name == "MlpPolicy":
         from .policy import MlpPolicy
         return MlpPolicy
-    if name in ("TapeSampler", "MppiPlanner"):
+    if name in ("TapeSampler", "MppiPlanner", "PolicyRolloutPlanner"):
         from . import planner
         return getattr(planner, name)
     raise AttributeError(name)

@@ -94,6 +94,8 @@ SYMBOLS = {
     "sbr_mppi_update": (C.c_int, [_VP, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, C.c_double, _I32, _VP, _VP, _VP]),
     "sbr_policy_param_count": (_I64, [_I32, _I32]),
     "sbr_rollout_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP]),
+    "sbr_lookahead_policy": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(SbrPolicy), _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                       _VP]),
     "sbr_reduce_stats": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
     "sbr_get_state": (C.c_int, [_VP, _VP, _VP, _VP]),
     "sbr_set_state": (C.c_int, [_VP, _VP, _VP, _VP]),

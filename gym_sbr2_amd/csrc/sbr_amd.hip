@@ -15,6 +15,8 @@
 //              softmax-weighted update of that tape with the candidates drawn again: no candidate tensor anywhere
 //   k_lookahead_tape_end, k_lookahead_sampled_end   the two fan-outs reporting where each branch ended - observation, state, done
 //              flag - for a terminal value on top of its return
+//   k_lookahead_policy   the policy kernel as a read-only fan-out: K closed-loop rollouts of the caller's MLP per env, each branch
+//              with exploration noise of its own, the handle and the observation untouched
 //   k_cycle_reset, k_cycle   the per-cycle env SBR-v2: one launch = one whole 12 h cycle (528 control intervals)
 //   k_export, k_import, k_m1_explicit   public <-> internal controller layout; implicit So[-1] / Sno[-1] made explicit
 //   k_stats    wavefront (DPP) reductions of a per-env vector -> {sum,min,max,count}
@@ -1564,6 +1566,128 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout_policy(SbrPar p, S
     store_record<OCI>(p, b, i0, l, rec);
     if (returns) returns[i] = acc;
 }
+
+// exploration noise of BRANCH k of a closed-loop lookahead (sbr_lookahead_policy): sbr_policy_noise's construction with k in the
+// upper 24 bits of the stream word, as sbr_tape_sample carries its candidate in stream 4.  k = 0 is sbr_policy_noise's block: the
+// same operations in the same order, so under -ffp-contract=off the same bits.  A function of its own: sbr_policy_noise and the
+// kernel that calls it stay as they are.
+SBR_DEV void sbr_branch_noise(uint64_t seed, uint64_t env_id, uint32_t k, uint32_t call, double& z0, double& z1) {
+    uint32_t c[4] = {call, 3u + 256u * k, (uint32_t)env_id, (uint32_t)(env_id >> 32)};
+    sbr_philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u1 = sbr_u53(c[0], c[1]), u2 = sbr_u53(c[2], c[3]);
+    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;
+    double sn, cs;
+    sincos(ang, &sn, &cs);
+    z0 = rad * cs; z1 = rad * sn;
+}
+// k_rollout_policy as a READ-ONLY fan-out (sbr_lookahead_policy): `fanout` closed-loop rollouts of the caller's policy per env,
+// each from the env's CURRENT plant, controller record and observation row, nothing of the handle and nothing of obs written.
+// One lane per BRANCH j = env * fanout + k.  The loop is k_rollout_policy's, REPEATED and not shared (see k_lookahead_tape_end:
+// the parent's instruction text stays what it is) - sbr_write_obs<float> before a decision with s > 0, sbr_mlp<H>,
+// sbr_run_intervals, sbr_finish_step with the register history - so without noise every branch returns the bits
+// k_rollout_policy returns for an env holding a copy of that state, and fed its own actions_out k_lookahead_tape returns the
+// same bits.  What is NOT here, for the reasons given at k_lookahead_tape: store_x / store_record, sbr_terminal, the return row,
+// the status bits and the plan.  The call count stays: it is the counter word of the noise.
+//  * Addressing: the env's rows - plant, record and the 18 observation values - by (e0, el) as in k_lookahead_tape, the mask on
+//    el included; the fanout lanes of an env share one fetch of each value.  The outputs are B wide and addressed by (j0, l).
+//  * Noise: sbr_branch_noise, branch k of the env; keep_mean = 1 leaves branch 0 of every env at the policy's mean (the value is
+//    not touched, rather than 0 added to it: -0 stays -0).
+//  * Population: the policy of a wave is its first lane's (readfirstlane below).
+//  * End outputs: sbr_store_branch_end behind the loop, each behind its wave-uniform NULL test.
+// n_steps = 0 (the host refuses it together with an end output): zeros in returns, nothing loaded.
+template <int H, bool OCI, int SCH, int WAVES>
+__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_policy(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
+                                                               uint32_t n_branch, const float* __restrict__ params, SbrPolicyDev pl,
+                                                               int32_t keep_mean, const float* __restrict__ obs,
+                                                               double* __restrict__ returns, double* __restrict__ rewards_out,
+                                                               float* __restrict__ actions_out, float* __restrict__ obs_end,
+                                                               float* __restrict__ state_end, uint8_t* __restrict__ done_end) {
+    const uint32_t l = threadIdx.x;
+    const uint32_t j0u = blockIdx.x * (uint32_t)SBR_BLOCK;   // n_branch < 2^31 (checked by the host): 32 bits hold every branch index
+    if (j0u + l >= n_branch) return;
+    const int64_t j0 = (int64_t)j0u;
+    if (n_steps == 0) {               // no call: nothing of the state, the observation or the net is loaded
+        if (returns) (returns + j0)[l] = 0.0;
+        return;
+    }
+    const uint32_t e0u = j0u / fanout;                       // the (e0, el) addressing of the env's rows: see k_lookahead_tape
+    const uint32_t eu = (j0u + l) / fanout;
+    const uint32_t el = (eu - e0u) & 511u;
+    const uint32_t k = j0u + l - eu * fanout;                // the lane's branch of its env
+    const int64_t e0 = (int64_t)e0u;
+    const uint64_t gid = (uint64_t)(b.first_env_id + e0) + el;
+    // the wave's policy block.  A population is cut at global ids that are multiples of 256 and the handle's first id is one
+    // (checked by the host), so a policy boundary falls at a local env index that is a multiple of 256, i.e. at branch index
+    // (multiple of 256) * fanout - a multiple of the workgroup size.  No workgroup of 256 branches, and so no wave, straddles
+    // two policies: the policy of the wave's first lane is the policy of all of them, whatever the fanout
+    const float* __restrict__ w = params;
+    if (pl.n_policies > 1) {
+        const uint32_t pol = __builtin_amdgcn_readfirstlane((uint32_t)(gid / (uint64_t)pl.envs_per_policy));
+        w = params + (int64_t)pol * pl.stride;
+    }
+    const bool noisy = pl.noise != 0 && !(keep_mean != 0 && k == 0);
+    double x[SBR_NX], xa6[SBR_NXD];
+    SbrX6Reg x6;                      // x6 and the ten Kla values stay in registers: see k_rollout
+    SbrRewardParts rp;
+    load_x(b, e0, el, x);
+    SbrRecord rec;
+    load_record<OCI>(p, b, e0, el, x[8], x[9], rec);
+    SbrCtl& c = rec.c;
+    bool done = rec.meta.done;
+    int32_t steps = rec.meta.steps;                // the branch's calls since reset: the counter word of its noise
+    float o[SBR_NOBS];
+    const float* __restrict__ env_obs = obs + e0 * SBR_NOBS + el * (uint32_t)SBR_NOBS;
+#pragma unroll
+    for (int q = 0; q < SBR_NOBS; ++q) o[q] = env_obs[q];
+    float a0 = 0.0f, a1 = 0.0f;
+    int32_t left = 1;                              // calls until the next decision, this one included
+    double acc = 0.0;
+    for (int32_t s = 0; s < n_steps; ++s) {
+        if (--left == 0) {                         // a decision call (wave-uniform): s % hold == 0
+            left = hold;
+            if (__builtin_amdgcn_ballot_w64(!done) != 0ull) {
+                if (s > 0) {
+                    x6.get(xa6);
+                    sbr_write_obs<float>(o, 1, c.t, x, xa6, x);
+                }
+                float y[2];
+                sbr_mlp<H>(pl, w, o, y);
+                if (pl.squash != 0) { y[0] = tanhf(y[0]); y[1] = tanhf(y[1]); }
+                a0 = __builtin_fmaf(pl.scale[0], y[0], pl.bias[0]);
+                a1 = __builtin_fmaf(pl.scale[1], y[1], pl.bias[1]);
+                if (pl.noise != 0) {
+                    double z0, z1;
+                    sbr_branch_noise(pl.seed, gid, k, (uint32_t)steps, z0, z1);
+                    if (noisy) {
+                        a0 = (float)((double)a0 + (double)pl.std[0] * z0);
+                        a1 = (float)((double)a1 + (double)pl.std[1] * z1);
+                    }
+                }
+            }
+            if (done) { a0 = 0.0f; a1 = 0.0f; }
+            if (actions_out) {
+                const int64_t row = (int64_t)(s / hold);
+                sbr_act2_f32 v; v.x = a0; v.y = a1;
+                *reinterpret_cast<sbr_act2_f32*>(actions_out + (row * n_branch + j0) * 2 + 2 * l) = v;
+            }
+        }
+        double r = 0.0;
+        if (!done) {
+            double t_obs;
+            bool dn;
+            sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
+            x6.get(xa6);
+            SbrHistReg hs{rec.hist};
+            r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, rec.qw, rec.ksum, rp);
+            acc += r;
+            steps = SbrMeta::next_steps(steps);
+            if (dn) done = true;
+        }
+        if (rewards_out) (rewards_out + ((int64_t)s * n_branch + j0))[l] = r;
+    }
+    if (returns) (returns + j0)[l] = acc;
+    sbr_store_branch_end(j0, l, done, c.t, x, x6, obs_end, state_end, done_end);
+}
 // ------------------------------------------------------------------------------------------- per-cycle env (SBR-v2)
 // SbrEnv2.reset (gym_SBR_env2.py:69-129): influent draw (scenario 0 by default, :104) and the 3-element observation built
 // from the sums of start state and influent.  CARRY keeps each env's current state as the start state (x0_new, :152).
@@ -2394,6 +2518,44 @@ int64_t sbr_policy_param_count(int32_t n_hidden, int32_t width) {
     return (SBR_NOBS * h + h) + (n_hidden == 2 ? h * h + h : 0) + (h * 2 + 2);
 }
 
+// What sbr_rollout_policy and sbr_lookahead_policy have to say about a policy; empty if it is valid.  Every check is evaluated,
+// the LAST failing one is reported.
+static std::string policy_error(const sbr_env* e, const sbr_policy* policy) {
+    if (!policy) return "NULL policy";
+    std::string bad;
+    const sbr_policy& q = *policy;
+    if (!q.params) bad = "NULL params";
+    if (q.n_hidden < 0 || q.n_hidden > 2) bad = "n_hidden must be 0, 1 or 2";
+    else if (q.n_hidden > 0 && q.width != 32 && q.width != 64) bad = "width must be 32 or 64";
+    if (q.activation != 0 && q.activation != 1) bad = "activation must be 0 (tanh) or 1 (relu)";
+    if (q.squash != 0 && q.squash != 1) bad = "squash must be 0 (none) or 1 (tanh)";
+    for (int k = 0; k < 2; ++k)
+        if (!(q.noise_std[k] >= 0.0f) || !std::isfinite(q.noise_std[k])) bad = "noise_std must be finite and >= 0";
+    if (q.n_policies < 1) bad = "n_policies must be >= 1";
+    else if (q.n_policies > 1) {
+        // a wave reads ONE policy block through the scalar data path: the population is cut at workgroup boundaries
+        if (q.envs_per_policy < SBR_BLOCK || q.envs_per_policy % SBR_BLOCK != 0)
+            bad = "with n_policies > 1 envs_per_policy must be a positive multiple of 256";
+        else if (e && e->buf.first_env_id % SBR_BLOCK != 0)
+            bad = "with n_policies > 1 the handle's first_env_id must be a multiple of 256";
+        else if (e && (e->buf.first_env_id < 0 || q.envs_per_policy > INT64_MAX / q.n_policies ||
+                       e->buf.first_env_id + e->n > q.n_policies * q.envs_per_policy))
+            bad = "the handle's envs reach past n_policies * envs_per_policy";
+    }
+    return bad;
+}
+// a validated sbr_policy as the kernels take it
+static SbrPolicyDev policy_dev(const sbr_policy* policy) {
+    SbrPolicyDev pl{};
+    pl.n_hidden = policy->n_hidden; pl.activation = policy->activation; pl.squash = policy->squash;
+    pl.noise = (policy->noise_std[0] != 0.0f || policy->noise_std[1] != 0.0f) ? 1 : 0;
+    pl.n_policies = policy->n_policies; pl.envs_per_policy = policy->envs_per_policy;
+    pl.stride = sbr_policy_param_count(policy->n_hidden, policy->width);
+    for (int k = 0; k < 2; ++k) { pl.scale[k] = policy->act_scale[k]; pl.bias[k] = policy->act_bias[k]; pl.std[k] = policy->noise_std[k]; }
+    pl.seed = policy->noise_seed;
+    return pl;
+}
+
 int sbr_rollout_policy(sbr_env* e, int32_t n_steps, int32_t hold, const sbr_policy* policy, float* obs, double* returns,
                        float* actions_out, double* rewards_out, void* stream) {
     // What the call has to say about its arguments; empty if they are valid.  Every check is evaluated, the LAST failing one is
@@ -2403,36 +2565,10 @@ int sbr_rollout_policy(sbr_env* e, int32_t n_steps, int32_t hold, const sbr_poli
     if (n_steps < 0) bad = "n_steps must be >= 0";
     if (hold < 1) bad = "hold must be >= 1";
     if (!obs) bad = "NULL obs";
-    if (!policy) bad = "NULL policy";
-    else {
-        const sbr_policy& q = *policy;
-        if (!q.params) bad = "NULL params";
-        if (q.n_hidden < 0 || q.n_hidden > 2) bad = "n_hidden must be 0, 1 or 2";
-        else if (q.n_hidden > 0 && q.width != 32 && q.width != 64) bad = "width must be 32 or 64";
-        if (q.activation != 0 && q.activation != 1) bad = "activation must be 0 (tanh) or 1 (relu)";
-        if (q.squash != 0 && q.squash != 1) bad = "squash must be 0 (none) or 1 (tanh)";
-        for (int k = 0; k < 2; ++k)
-            if (!(q.noise_std[k] >= 0.0f) || !std::isfinite(q.noise_std[k])) bad = "noise_std must be finite and >= 0";
-        if (q.n_policies < 1) bad = "n_policies must be >= 1";
-        else if (q.n_policies > 1) {
-            // a wave reads ONE policy block through the scalar data path: the population is cut at workgroup boundaries
-            if (q.envs_per_policy < SBR_BLOCK || q.envs_per_policy % SBR_BLOCK != 0)
-                bad = "with n_policies > 1 envs_per_policy must be a positive multiple of 256";
-            else if (e && e->buf.first_env_id % SBR_BLOCK != 0)
-                bad = "with n_policies > 1 the handle's first_env_id must be a multiple of 256";
-            else if (e && (e->buf.first_env_id < 0 || q.envs_per_policy > INT64_MAX / q.n_policies ||
-                           e->buf.first_env_id + e->n > q.n_policies * q.envs_per_policy))
-                bad = "the handle's envs reach past n_policies * envs_per_policy";
-        }
-    }
+    const std::string pb = policy_error(e, policy);
+    if (!pb.empty()) bad = pb;
     if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_rollout_policy: " + bad);
-    SbrPolicyDev pl{};
-    pl.n_hidden = policy->n_hidden; pl.activation = policy->activation; pl.squash = policy->squash;
-    pl.noise = (policy->noise_std[0] != 0.0f || policy->noise_std[1] != 0.0f) ? 1 : 0;
-    pl.n_policies = policy->n_policies; pl.envs_per_policy = policy->envs_per_policy;
-    pl.stride = sbr_policy_param_count(policy->n_hidden, policy->width);
-    for (int k = 0; k < 2; ++k) { pl.scale[k] = policy->act_scale[k]; pl.bias[k] = policy->act_bias[k]; pl.std[k] = policy->noise_std[k]; }
-    pl.seed = policy->noise_seed;
+    const SbrPolicyDev pl = policy_dev(policy);
     const bool wide = policy->n_hidden > 0 && policy->width == 64;     // without a hidden layer the width does not matter
     return launched(e, [&] {
         dispatch(e, [&](auto c) {
@@ -2444,6 +2580,44 @@ int sbr_rollout_policy(sbr_env* e, int32_t n_steps, int32_t hold, const sbr_poli
                                    policy->params, pl, obs, returns, actions_out, rewards_out);
             });
         });
+    });
+}
+
+int sbr_lookahead_policy(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const sbr_policy* policy, int32_t keep_mean,
+                         const float* obs, double* returns, double* rewards_out, int32_t* best_index, double* best_return,
+                         float* actions_out, float* obs_end, float* state_end, uint8_t* done_end, void* stream) {
+    // Every check is evaluated, the LAST failing one is reported - all of them before anything is touched.
+    std::string bad;
+    if (!e) bad = "NULL env";
+    if (n_steps < 0) bad = "n_steps must be >= 0";
+    else if (n_steps == 0 && (obs_end || state_end || done_end))
+        bad = "n_steps = 0 has no end state to report that the handle does not already hold";
+    if (hold < 1) bad = "hold must be >= 1";
+    if (fanout < 1) bad = "fanout must be >= 1";
+    else if (fanout > (1 << 24)) bad = "fanout must be <= 2^24 (the branch is 24 bits of the Philox stream word)";
+    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+    if (keep_mean != 0 && keep_mean != 1) bad = "keep_mean must be 0 or 1";
+    if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
+    if (!obs) bad = "NULL obs";
+    const std::string pb = policy_error(e, policy);
+    if (!pb.empty()) bad = pb;
+    if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_lookahead_policy: " + bad);
+    const SbrPolicyDev pl = policy_dev(policy);
+    const bool wide = policy->n_hidden > 0 && policy->width == 64;     // without a hidden layer the width does not matter
+    const int64_t nb = e->n * (int64_t)fanout;
+    return launched(e, [&] {
+        dispatch(e, [&](auto c) {
+            using C = decltype(c);
+            either(wide, [&](auto w64) {
+                constexpr int H = decltype(w64)::value ? 64 : 32;
+                // the register budget goes by the branches, as in sbr_lookahead_actions
+                const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_policy<H, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_policy<H, C::OCI, C::SCH, 2>;
+                hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
+                                   (uint32_t)nb, policy->params, pl, keep_mean, obs, returns, rewards_out, actions_out, obs_end, state_end,
+                                   done_end);
+            });
+        });
+        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
 }
 

@@ -48,6 +48,9 @@ class SbrEnv2Vec(SbrOSVec):
     def lookahead_sampled_end(self, *a, **k):
         raise NotImplementedError("the sampled lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 
+    def lookahead_policy(self, *a, **k):
+        raise NotImplementedError("the closed-loop lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
     def branch_best(self, *a, **k):
         raise NotImplementedError("the winner of a lookahead's branches belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 

@@ -1,7 +1,9 @@
-"""Sampling planners on the fused lookahead: the sampler of candidate tapes (struct sbr_sampler) and a thin MPPI loop.
+"""Sampling planners on the fused lookahead: the sampler of candidate tapes (struct sbr_sampler), a thin MPPI loop and a thin
+policy-rollout planner on the closed-loop lookahead.
 
-Plumbing only: the candidates are drawn, scored and averaged inside libsbr_amd.so (sbr_lookahead_sampled, sbr_mppi_update);
-nothing here does arithmetic on a candidate.  The one sum formed here adds the caller's terminal value to a return."""
+Plumbing only: the candidates are drawn, scored and averaged inside libsbr_amd.so (sbr_lookahead_sampled, sbr_mppi_update,
+sbr_lookahead_policy); nothing here does arithmetic on a candidate.  The sums formed here add the caller's terminal value to a
+return and average an env's returns."""
 import ctypes as C
 
 import numpy as np
@@ -89,3 +91,41 @@ class MppiPlanner:
         self.nominal = buf[1:]
         self.decision += 1
         return (buf[0], ret) if return_returns else buf[0]
+
+
+class PolicyRolloutPlanner:
+    """Policy-guided planning on the closed-loop lookahead: per decision, `fanout` rollouts of `policy` (an MlpPolicy) over
+    `n_steps` calls are run from every env's current state and observation (lookahead_policy, the handle untouched), branch 0
+    at the policy's mean and the others under exploration noise of std `noise_std`; the first action of the best branch is the
+    plan, and the mean of the env's returns is a Monte-Carlo estimate of the policy's value at that state.  Decision d draws
+    under noise_seed + d.  `env` is an SbrOSVec or a ShardedSbrOS.
+
+        planner = PolicyRolloutPlanner(env, policy, fanout=64, n_steps=50, hold=1, noise_std=(0.3, 2.0))
+        while ...:
+            action, value = planner.plan()
+            env.step(action)
+
+    terminal_value: a callable taking (obs_end [N, K, 18], state_end [N, K, 15]), float32, and returning a tensor [N, K] - the
+    caller's critic.  Each branch is then scored by return + where(done_end, 0, terminal_value(...)), and the value is the mean
+    of those scores.  Nothing on the path waits for the device."""
+
+    def __init__(self, env, policy, fanout, n_steps, hold, noise_std, terminal_value=None, noise_seed=0):
+        self.env, self.policy, self.fanout, self.n_steps, self.hold = env, policy, int(fanout), int(n_steps), int(hold)
+        self.noise_std, self.terminal_value, self.noise_seed, self.decision = noise_std, terminal_value, int(noise_seed), 0
+
+    def plan(self, obs=None):
+        """One decision: (the action [N, 2] float32 to give to step(), the Monte-Carlo value [N] float64).  `obs` is the
+        observation in force (None: the env's own obs buffer)."""
+        end = self.terminal_value is not None
+        out = self.env.lookahead_policy(self.policy, self.fanout, self.n_steps, hold=self.hold, obs=obs, noise_std=self.noise_std,
+                                        noise_seed=self.noise_seed + self.decision, keep_mean=True, return_actions=True,
+                                        return_end=end)
+        ret, acts = out[0], out[1]
+        if end:
+            obs_end, state_end, done_end = out[2:]
+            v = self.terminal_value(obs_end, state_end).double()
+            ret = (ret + v.masked_fill(done_end, 0.0)).contiguous()
+        best, _ = self.env.branch_best(ret)
+        self.decision += 1
+        pick = best.long()[:, None, None].expand(-1, 1, 2)
+        return acts[0].gather(1, pick)[:, 0], ret.mean(dim=1)

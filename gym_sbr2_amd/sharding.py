@@ -148,6 +148,15 @@ class ShardedSbrOS:
         return self.env.rollout_policy(policy, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed,
                                        return_actions=return_actions, return_rewards=return_rewards)
 
+    def lookahead_policy(self, policy, fanout, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, keep_mean=False,
+                         return_rewards=False, return_best=False, return_actions=False, return_end=False):
+        """SbrOSVec.lookahead_policy for this rank's block (`obs` [n_local, 18] and every result are the rank's own slices).
+        `policy` is the WHOLE population on every rank, as in rollout_policy; the noise of a branch is keyed by its env's global
+        id and its index among the env's branches, so the results do not depend on the world size."""
+        return self.env.lookahead_policy(policy, fanout, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed,
+                                         keep_mean=keep_mean, return_rewards=return_rewards, return_best=return_best,
+                                         return_actions=return_actions, return_end=return_end)
+
     def gather_buffers(self, dtype=torch.float32):
         """Caller-owned buffers for gather_episode_returns_into(): (float64 row [n_local], send [n_local] dtype, recv [n_global]
         dtype) on this rank's device.  Only equal shards can be gathered without staging (all_gather_into_tensor)."""

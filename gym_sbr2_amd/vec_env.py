@@ -418,6 +418,46 @@ class SbrOSVec:
             self.obs.copy_(torch.where(live[:, None], o.to(self.obs.dtype), self.obs))
         return _one_or_all((ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ()))
 
+    def lookahead_policy(self, policy, fanout, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, keep_mean=False,
+                         return_rewards=False, return_best=False, return_actions=False, return_end=False):
+        """Read-only lookahead in CLOSED loop, one launch (sbr_lookahead_policy): `fanout` rollouts of `policy` (an MlpPolicy or
+        a population) per env, each from the env's CURRENT state and its row of `obs` [N, 18] float32 (obs=None: self.obs,
+        converted to float32 if the handle's outputs are float64), decisions every `hold` calls as in rollout_policy.  The handle
+        and obs are left bit for bit as they were; nothing is copied back.  With noise_std, branch k of an env draws noise of its
+        own, keyed by noise_seed, the global env id, k and the branch's call count - branch 0 what rollout_policy would draw;
+        keep_mean=True runs branch 0 of every env without noise.  Returns the sum of this launch's rewards per branch [N, K]
+        float64, then, in this order and only if asked for: the reward of every call [n_steps, N, K] float64; best_index [N]
+        int32 and best_return [N] float64 (lookahead's rule); the decisions [ceil(n_steps/hold), N, K, 2] float32 exactly as
+        they were integrated (fed to lookahead they give the same bits); obs_end [N, K, 18], state_end [N, K, 15] and done_end
+        [N, K] as lookahead_end gives them (n_steps = 0 is then refused)."""
+        n_steps, hold, fanout = int(n_steps), int(hold), int(fanout)
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        if n_steps < 0:
+            raise ValueError("n_steps must be >= 0")
+        n, dev = self.num_envs, self.device
+        if fanout < 1 or fanout > 2 ** 24 or n * fanout >= 2 ** 31:      # before the outputs are sized by it
+            raise ValueError("fanout must be in 1 .. 2^24 with num_envs * fanout below 2^31")
+        o = self.obs if obs is None else obs
+        if obs is None and o.dtype != torch.float32:
+            o = o.to(torch.float32)
+        if not (isinstance(o, torch.Tensor) and o.dtype == torch.float32 and o.device == dev and o.is_contiguous()
+                and tuple(o.shape) == (n, _capi.NOBS)):
+            raise ValueError("obs must be a contiguous float32 tensor of shape [N,%d] on %s" % (_capi.NOBS, dev))
+        pol = policy.c_struct(dev, noise_std=noise_std, noise_seed=noise_seed)
+        self._keep_p = (policy, pol, o)
+        ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
+        rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
+        bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
+        br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
+        acts = torch.empty((-(-n_steps // hold), n, fanout, 2), dtype=torch.float32, device=dev) if return_actions else None
+        ends = self._end_outputs(fanout) if return_end else (None, None, None)
+        _capi.check(self.lib.sbr_lookahead_policy(self._h, n_steps, hold, fanout, C.byref(pol), 1 if keep_mean else 0, _ptr(o),
+                                                  _ptr(ret), _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts), *[_ptr(t) for t in ends],
+                                                  self._stream()), self._h)
+        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ())
+                           + ((acts,) if return_actions else ()) + (ends if return_end else ()))
+
     def enable_trace(self, n_envs=1, capacity=463):
         """Trajectory export: every step() appends one record (_capi.TR_*: t, x(14), Kla, EC, reward, done, the set-points in
         force, the NO3-PID's e/ie/dcv and the four reward diagnostics) for the first n_envs envs at index = calls since

@@ -463,6 +463,49 @@ int64_t sbr_policy_param_count(int32_t n_hidden, int32_t width);
 int sbr_rollout_policy(sbr_env* env, int32_t n_steps, int32_t hold, const sbr_policy* policy, float* obs, double* returns,
                        float* actions_out, double* rewards_out, void* stream);
 
+/* CLOSED-LOOP lookahead: `fanout` rollouts of the caller's policy per env, each from the env's CURRENT state and observation, the
+ * handle left bit for bit as it was (Monte-Carlo value and advantage estimates at the states the learner visits, policy-guided
+ * MPC, n-step returns plus a critic on obs_end).  sbr_rollout_policy in the read-only, K-branches-per-env form of
+ * sbr_lookahead_actions.
+ * A BRANCH is j = i*fanout + k: env i, branch k; there are B = N*fanout < 2^31 of them.  Branch j starts from env i's plant and
+ * controller record as they are - also in the form sbr_step leaves them - and from env i's row of obs, and runs exactly the
+ * calls sbr_rollout_policy would run on an env in that state under that policy: a decision on the calls s of this launch with
+ * s % hold == 0, the same float32 arithmetic of the net, the same clipping.  Without noise every branch of an env returns the
+ * bits sbr_rollout_policy returns for a copy of the env; fed this call's actions_out, sbr_lookahead_actions(_end) returns the
+ * same bits in returns, rewards_out, best_* and the end outputs.
+ *   policy      as in sbr_rollout_policy.  A population: the policy of a branch is its ENV's, global id g / envs_per_policy.
+ *               With n_policies > 1 the conditions of sbr_rollout_policy apply unchanged (envs_per_policy and the handle's
+ *               first_env_id multiples of 256) and are enough for any fanout: a policy boundary then falls at a branch index
+ *               (multiple of 256)*fanout, so no workgroup of 256 branches straddles two policies.
+ *   noise       with noise_std != 0 the noise of branch k is the Box-Muller pair of the Philox4x32-10 block keyed by noise_seed
+ *               with counter = (the BRANCH's calls since reset, 3 + 256*k, g_lo, g_hi): sbr_rollout_policy's construction with
+ *               k in the upper 24 bits of the stream word (as the sampler carries its candidate in stream 4), hence
+ *               fanout <= 2^24.  Branch 0 draws exactly what sbr_rollout_policy would draw next for that env.  The noise
+ *               depends on (noise_seed, g, k, call count) and on nothing else: not on N, fanout or the shard.
+ *   keep_mean   1: branch 0 of every env runs WITHOUT noise - the policy's mean action, the closed-loop counterpart of the
+ *               sampler's keep_nominal; the other branches are unchanged.  0 or 1.
+ *   obs         [N][18] float32, DEVICE pointer, const: the observation in force of every env (what sbr_reset, sbr_step or
+ *               sbr_rollout_policy last left for it), shared by the env's branches and NOT written
+ *   returns     [B] float64 or NULL: sum of the launch's rewards of the branch, added in call order
+ *   rewards_out [n_steps][B] float64 or NULL: the reward of every call; 0.0 for a call the branch skipped
+ *   best_index  [N] int32 or NULL, best_return [N] float64 or NULL: the winner among each env's returns under the rule of
+ *               sbr_lookahead_actions, reduced FROM `returns` by a second kernel on the same stream: give returns with them
+ *   actions_out [ceil(n_steps / hold)][B][2] float32 or NULL: row s / hold is the decision of call s, exactly the value that is
+ *               cast to double and integrated; 0 for a decision a branch skipped because its episode had ended
+ *   obs_end     [B][SBR_NOBS] float32, state_end [B][SBR_NSTATE] float32, done_end [B] uint8, each or NULL: where the branch
+ *               ended, under the words of sbr_lookahead_actions_end - float32 whatever cfg.out_f64 says, zeros for a done branch
+ * NOTHING of the handle is written and obs is not written; nothing is allocated (graph-capturable).  No terminal phases run
+ * (they change only state that is discarded here); the end-of-cycle reward of reward_kind 2 is part of the done call and is
+ * included.  The register budget of the launch goes by B, not by N.  n_steps = 0 writes returns = 0, best_index = 0 and
+ * best_return = 0 and reads nothing.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): every policy refusal of
+ * sbr_rollout_policy; NULL env, policy or obs; n_steps < 0; hold < 1; fanout < 1 or > 2^24; N*fanout >= 2^31; keep_mean other
+ * than 0 or 1; best_index or best_return given while returns is NULL; obs_end, state_end or done_end given with n_steps = 0. */
+int sbr_lookahead_policy(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const sbr_policy* policy,
+                         int32_t keep_mean, const float* obs, double* returns, double* rewards_out,
+                         int32_t* best_index, double* best_return, float* actions_out,
+                         float* obs_end, float* state_end, uint8_t* done_end, void* stream);
+
 /* batch statistics of a per-env float64 vector (e.g. episode returns): wavefront reductions
  * + one atomic per wave.  out4 = {sum, min, max, count} float64, DEVICE pointer. */
 int sbr_reduce_stats(sbr_env* env, const double* values, int64_t n, double* out4, void* stream);
