@@ -981,10 +981,48 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout_tape(SbrPar p, Sbr
     if (returns) returns[i] = acc;
 }
 
-// k_rollout_tape as a READ-ONLY fan-out (sbr_lookahead_actions): `fanout` tapes per env, each played from the env's CURRENT plant
-// and controller record, and nothing of the handle written.  One lane per BRANCH j = env * fanout + candidate; the loop body is
-// the tape kernel's - sbr_run_intervals, sbr_finish_step with the register history, a done branch skips - so branch j returns
-// the bits k_rollout_tape returns for an env holding a copy of that state and fed column j of the tape.
+// Where a branch ENDED (sbr_lookahead_actions_end / sbr_lookahead_sampled_end), for a terminal value on top of its return: stored
+// once per launch and branch, behind the loop.  Each output is optional (wave-uniform tests).  A branch that is not done: the
+// rows k_step forms for a call that does not end the episode - sbr_write_obs / sbr_write_state of the plant, the last interval's
+// start values (x6) and the running time c.t, which is sbr_finish_step's t_obs for such a call - the observation as
+// k_rollout_policy writes it back on exit.  A done branch (on entry or during the launch): zeros; its plant stopped at the done
+// call without the terminal phases, a state no other entry point reports.  float32 whatever cfg.out_f64 says, like the policy
+// kernel's observation.  Plain per-lane stores, 72 and 60 bytes per lane at a lane stride of 72 and 60: the wave's rows are
+// contiguous, so every byte of the lines it touches is written.  The 18 + 15 stores of the source are adjacent, and the backend
+// merges them into 16-byte ones (5 per obs_end row, 4 per state_end row; DESIGN.md section 3.6) - once per launch, not per call,
+// where k_step transposes its rows through LDS on every call.
+SBR_DEV void sbr_store_branch_end(int64_t j0, uint32_t l, bool done, double t, const double (&x)[SBR_NX], const SbrX6Reg& x6,
+                                  float* __restrict__ obs_end, float* __restrict__ state_end, uint8_t* __restrict__ done_end) {
+    if (done_end) (done_end + j0)[l] = (uint8_t)(done ? 1 : 0);
+    if (obs_end) {
+        float o[SBR_NOBS];
+#pragma unroll
+        for (int k = 0; k < SBR_NOBS; ++k) o[k] = 0.0f;
+        if (!done) {
+            double xa6[SBR_NXD];
+            x6.get(xa6);
+            sbr_write_obs<float>(o, 1, t, x, xa6, x);
+        }
+        float* mine = obs_end + j0 * SBR_NOBS + l * (uint32_t)SBR_NOBS;
+#pragma unroll
+        for (int k = 0; k < SBR_NOBS; ++k) mine[k] = o[k];
+    }
+    if (state_end) {
+        float sv[SBR_NSTATE];
+#pragma unroll
+        for (int k = 0; k < SBR_NSTATE; ++k) sv[k] = 0.0f;
+        if (!done) sbr_write_state<float>(sv, 1, t, x);
+        float* mine = state_end + j0 * SBR_NSTATE + l * (uint32_t)SBR_NSTATE;
+#pragma unroll
+        for (int k = 0; k < SBR_NSTATE; ++k) mine[k] = sv[k];
+    }
+}
+
+// k_rollout_tape as a READ-ONLY fan-out (sbr_lookahead_actions, sbr_lookahead_actions_end): `fanout` tapes per env, each played
+// from the env's CURRENT plant and controller record, and nothing of the handle written.  One lane per BRANCH j = env * fanout +
+// candidate; the loop body is the tape kernel's - sbr_run_intervals, sbr_finish_step with the register history, a done branch
+// skips - so branch j returns the bits k_rollout_tape returns for an env holding a copy of that state and fed column j of the
+// tape.
 // What is NOT here, and why that changes no returned bit:
 //  * store_x / store_record: the branch's end state is discarded;
 //  * sbr_terminal: settle, draw and idle after the done call move only x and Qw, which nothing reads afterwards (a finished branch
@@ -995,17 +1033,23 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_rollout_tape(SbrPar p, Sbr
 // bits).  load_x / load_record take that pair where the other kernels pass (i0, l): every row stays a scalar base plus one
 // 32-bit lane offset, and lanes of one env coalesce into one fetch of its 8 bytes.  The tape and the outputs
 // are B = N * fanout wide and addressed by (j0, l) like the tape kernel's.
-template <typename ActT, bool OCI, int SCH, int WAVES>
-__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_tape(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
-                                                             uint32_t n_branch, const ActT* __restrict__ actions,
-                                                             double* __restrict__ returns, double* __restrict__ rewards_out) {
+// END: the build that also reports where each branch ended (sbr_store_branch_end), k_lookahead_tape_end.  It has no n_steps = 0
+// path: the host refuses that (the handle already holds the state).  Two kernels over the one body and not a run-time test: the
+// tests address each by its mangled name and pin its registers and its store count, and a caller that wants no end state pays
+// nothing for one.  p and b by value: through references every build came out 80 - 190 instructions longer.
+template <bool END, typename ActT, bool OCI, int SCH>
+SBR_DEV void sbr_lookahead_tape(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout, uint32_t n_branch,
+                                const ActT* __restrict__ actions, double* __restrict__ returns, double* __restrict__ rewards_out,
+                                float* __restrict__ obs_end, float* __restrict__ state_end, uint8_t* __restrict__ done_end) {
     const uint32_t l = threadIdx.x;
     const uint32_t j0u = blockIdx.x * (uint32_t)SBR_BLOCK;   // n_branch < 2^31 (checked by the host): 32 bits hold every branch index
     if (j0u + l >= n_branch) return;
     const int64_t j0 = (int64_t)j0u;
-    if (n_steps == 0) {               // no call: nothing of the state is loaded
-        if (returns) (returns + j0)[l] = 0.0;
-        return;
+    if constexpr (!END) {
+        if (n_steps == 0) {           // no call: nothing of the state is loaded
+            if (returns) (returns + j0)[l] = 0.0;
+            return;
+        }
     }
     const uint32_t e0u = j0u / fanout;                       // wave-uniform: one scalar division per launch
     // el <= l / fanout + 1 <= 256.  The mask changes no value; it tells the backend that el * 8 fits 32 bits, which is what lets
@@ -1046,6 +1090,21 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_tape(SbrPar p, S
         a0 = n0; a1 = n1;
     }
     if (returns) (returns + j0)[l] = acc;
+    if constexpr (END) sbr_store_branch_end(j0, l, done, c.t, x, x6, obs_end, state_end, done_end);
+}
+template <typename ActT, bool OCI, int SCH, int WAVES>
+__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_tape(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
+                                                             uint32_t n_branch, const ActT* __restrict__ actions,
+                                                             double* __restrict__ returns, double* __restrict__ rewards_out) {
+    sbr_lookahead_tape<false, ActT, OCI, SCH>(p, b, n_steps, hold, fanout, n_branch, actions, returns, rewards_out, nullptr, nullptr, nullptr);
+}
+template <typename ActT, bool OCI, int SCH, int WAVES>
+__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_tape_end(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
+                                                                 uint32_t n_branch, const ActT* __restrict__ actions,
+                                                                 double* __restrict__ returns, double* __restrict__ rewards_out,
+                                                                 float* __restrict__ obs_end, float* __restrict__ state_end,
+                                                                 uint8_t* __restrict__ done_end) {
+    sbr_lookahead_tape<true, ActT, OCI, SCH>(p, b, n_steps, hold, fanout, n_branch, actions, returns, rewards_out, obs_end, state_end, done_end);
 }
 
 // The winner of each env's `fanout` branch returns (sbr_lookahead_actions, launched behind k_lookahead_tape on the same stream):
@@ -1154,100 +1213,9 @@ __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_sampled(SbrPar p
     if (returns) (returns + j0)[l] = acc;
 }
 
-// Where a branch ENDED (sbr_lookahead_actions_end / sbr_lookahead_sampled_end), for a terminal value on top of its return: stored
-// once per launch and branch, behind the loop.  Each output is optional (wave-uniform tests).  A branch that is not done: the
-// rows k_step forms for a call that does not end the episode - sbr_write_obs / sbr_write_state of the plant, the last interval's
-// start values (x6) and the running time c.t, which is sbr_finish_step's t_obs for such a call - the observation as
-// k_rollout_policy writes it back on exit.  A done branch (on entry or during the launch): zeros; its plant stopped at the done
-// call without the terminal phases, a state no other entry point reports.  float32 whatever cfg.out_f64 says, like the policy
-// kernel's observation.  Plain per-lane stores, 72 and 60 bytes per lane at a lane stride of 72 and 60: the wave's rows are
-// contiguous, so every byte of the lines it touches is written.  The 18 + 15 stores of the source are adjacent, and the backend
-// merges them into 16-byte ones (5 per obs_end row, 4 per state_end row; DESIGN.md section 3.6) - once per launch, not per call,
-// where k_step transposes its rows through LDS on every call.
-SBR_DEV void sbr_store_branch_end(int64_t j0, uint32_t l, bool done, double t, const double (&x)[SBR_NX], const SbrX6Reg& x6,
-                                  float* __restrict__ obs_end, float* __restrict__ state_end, uint8_t* __restrict__ done_end) {
-    if (done_end) (done_end + j0)[l] = (uint8_t)(done ? 1 : 0);
-    if (obs_end) {
-        float o[SBR_NOBS];
-#pragma unroll
-        for (int k = 0; k < SBR_NOBS; ++k) o[k] = 0.0f;
-        if (!done) {
-            double xa6[SBR_NXD];
-            x6.get(xa6);
-            sbr_write_obs<float>(o, 1, t, x, xa6, x);
-        }
-        float* mine = obs_end + j0 * SBR_NOBS + l * (uint32_t)SBR_NOBS;
-#pragma unroll
-        for (int k = 0; k < SBR_NOBS; ++k) mine[k] = o[k];
-    }
-    if (state_end) {
-        float sv[SBR_NSTATE];
-#pragma unroll
-        for (int k = 0; k < SBR_NSTATE; ++k) sv[k] = 0.0f;
-        if (!done) sbr_write_state<float>(sv, 1, t, x);
-        float* mine = state_end + j0 * SBR_NSTATE + l * (uint32_t)SBR_NSTATE;
-#pragma unroll
-        for (int k = 0; k < SBR_NSTATE; ++k) mine[k] = sv[k];
-    }
-}
-
-// k_lookahead_tape that also reports where each branch ended.  A kernel of its own and not a parameter of k_lookahead_tape: the
-// tests address that kernel by its mangled name and pin its registers and its store count, and a caller that wants no end state
-// pays nothing for this one.  The loop is REPEATED, not shared: moving the parent's loop into a device function would be a
-// change to the parent, and its instruction text is to stay what it is.  Same arithmetic on the same values in the same order,
-// so returns and rewards_out are the parent's bits.  n_steps >= 1 (the host refuses 0: the handle already holds that state).
-template <typename ActT, bool OCI, int SCH, int WAVES>
-__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_tape_end(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
-                                                                 uint32_t n_branch, const ActT* __restrict__ actions,
-                                                                 double* __restrict__ returns, double* __restrict__ rewards_out,
-                                                                 float* __restrict__ obs_end, float* __restrict__ state_end,
-                                                                 uint8_t* __restrict__ done_end) {
-    const uint32_t l = threadIdx.x;
-    const uint32_t j0u = blockIdx.x * (uint32_t)SBR_BLOCK;   // n_branch < 2^31 (checked by the host): 32 bits hold every branch index
-    if (j0u + l >= n_branch) return;
-    const int64_t j0 = (int64_t)j0u;
-    const uint32_t e0u = j0u / fanout;                       // the (e0, el) addressing of the env's rows: see k_lookahead_tape
-    const uint32_t el = ((j0u + l) / fanout - e0u) & 511u;
-    const int64_t e0 = (int64_t)e0u;
-    double x[SBR_NX], xa6[SBR_NXD];
-    SbrX6Reg x6;
-    SbrRewardParts rp;
-    load_x(b, e0, el, x);
-    SbrRecord rec;
-    load_record<OCI>(p, b, e0, el, x[8], x[9], rec);
-    SbrCtl& c = rec.c;
-    bool done = rec.meta.done;
-    const ActT* row = actions + j0 * 2;
-    ActT a0, a1;
-    tape_load(row, l, a0, a1);
-    int32_t left = hold;
-    double acc = 0.0;
-    for (int32_t s = 0; s < n_steps; ++s) {
-        ActT n0 = a0, n1 = a1;
-        if (--left == 0 && s + 1 < n_steps) {
-            row += (int64_t)n_branch * 2; left = hold;
-            tape_load(row, l, n0, n1);
-        }
-        double r = 0.0;
-        if (!done) {
-            double t_obs;
-            bool dn;
-            sbr_run_intervals<SCH>(p, c, x, (double)a0, (double)a1, x6, SbrNoTrace{});
-            x6.get(xa6);
-            SbrHistReg hs{rec.hist};
-            r = sbr_finish_step<OCI, SCH, SbrHistReg, false>(p, c, hs, x, xa6, t_obs, dn, rec.qw, rec.ksum, rp);
-            acc += r;
-            if (dn) done = true;
-        }
-        if (rewards_out) (rewards_out + ((int64_t)s * n_branch + j0))[l] = r;
-        a0 = n0; a1 = n1;
-    }
-    if (returns) (returns + j0)[l] = acc;
-    sbr_store_branch_end(j0, l, done, c.t, x, x6, obs_end, state_end, done_end);
-}
-
-// k_lookahead_sampled that also reports where each branch ended: its loop repeated, for the reasons given at
-// k_lookahead_tape_end, with sbr_tape_sample at its one site.
+// k_lookahead_sampled that also reports where each branch ended.  Its body is k_lookahead_sampled's REPEATED, and not one body
+// under two kernels like sbr_lookahead_tape: merged that way one of the 24 builds (float32 tape, operating-cost reward, scheme 0)
+// spilled four more scalar registers and grew by 24 instructions (profiles/r14_fused_isa.txt).
 template <typename ActT, bool OCI, int SCH, int WAVES>
 __global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_lookahead_sampled_end(SbrPar p, SbrBuf b, int32_t n_steps, int32_t hold, uint32_t fanout,
                                                                     uint32_t n_branch, const ActT* __restrict__ nominal, sbr_sampler sm,
@@ -1582,8 +1550,9 @@ SBR_DEV void sbr_branch_noise(uint64_t seed, uint64_t env_id, uint32_t k, uint32
 }
 // k_rollout_policy as a READ-ONLY fan-out (sbr_lookahead_policy): `fanout` closed-loop rollouts of the caller's policy per env,
 // each from the env's CURRENT plant, controller record and observation row, nothing of the handle and nothing of obs written.
-// One lane per BRANCH j = env * fanout + k.  The loop is k_rollout_policy's, REPEATED and not shared (see k_lookahead_tape_end:
-// the parent's instruction text stays what it is) - sbr_write_obs<float> before a decision with s > 0, sbr_mlp<H>,
+// One lane per BRANCH j = env * fanout + k.  The loop is k_rollout_policy's, REPEATED and not shared (DESIGN.md section 3.6:
+// shared through device functions it moved registers, spills or scratch of both kernels' builds, profiles/r14_fused_isa.txt) -
+// sbr_write_obs<float> before a decision with s > 0, sbr_mlp<H>,
 // sbr_run_intervals, sbr_finish_step with the register history - so without noise every branch returns the bits
 // k_rollout_policy returns for an env holding a copy of that state, and fed its own actions_out k_lookahead_tape returns the
 // same bits.  What is NOT here, for the reasons given at k_lookahead_tape: store_x / store_record, sbr_terminal, the return row,
@@ -2059,8 +2028,16 @@ template <typename F> static void dispatch(const sbr_env* e, F&& f) {
     }); });
 }
 
-// the fused kernels (k_cycle, k_rollout): scheme 0 has no one-wave build (fused_waves is 2 for it)
+// the fused kernels (k_cycle, k_rollout and the kernels behind it): scheme 0 has no one-wave build (fused_waves is 2 for it)
 template <int SCH> constexpr int kFusedOneWave = SCH == 1 ? 1 : 2;
+// The launch of a fused kernel over `lanes` lanes: the handle's envs, or the branches of a lookahead - the register budget goes by
+// the lanes of THE launch.  kernel(w) names the build for decltype(w)::value waves per SIMD; e->par and e->buf lead its arguments.
+template <int SCH, typename Kernel, typename... Args>
+static void launch_fused(const sbr_env* e, int64_t lanes, void* stream, Kernel&& kernel, Args... args) {
+    const auto fn = fused_waves_for(e, lanes) == 1 ? kernel(std::integral_constant<int, kFusedOneWave<SCH>>{})
+                                                   : kernel(std::integral_constant<int, 2>{});
+    hipLaunchKernelGGL(fn, grid_for(lanes), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, args...);
+}
 
 // What sbr_create has to say about a config; empty if it is valid.  Every check is evaluated and the LAST failing one is reported.
 static std::string config_error(const sbr_config& c) {
@@ -2308,9 +2285,8 @@ int sbr_cycle_step(sbr_env* e, const void* action, void* obs, void* reward, doub
             using C = decltype(c);
             using T = typename C::OutT;
             using A = typename C::ActT;
-            const auto fn = fused_waves(e) == 1 ? k_cycle<T, A, C::SCH, kFusedOneWave<C::SCH>> : k_cycle<T, A, C::SCH, 2>;
-            hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, (const A*)action, (T*)obs,
-                               (T*)reward, diag);
+            launch_fused<C::SCH>(e, e->n, stream, [](auto w) { return k_cycle<T, A, C::SCH, decltype(w)::value>; }, (const A*)action,
+                                 (T*)obs, (T*)reward, diag);
         });
     });
 }
@@ -2320,9 +2296,8 @@ int sbr_rollout(sbr_env* e, int32_t n_steps, uint64_t policy_seed, double* retur
     return launched(e, [&] {
         dispatch(e, [&](auto c) {
             using C = decltype(c);
-            const auto fn = fused_waves(e) == 1 ? k_rollout<C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_rollout<C::OCI, C::SCH, 2>;
-            hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, policy_seed,
-                               returns, actions_out);
+            launch_fused<C::SCH>(e, e->n, stream, [](auto w) { return k_rollout<C::OCI, C::SCH, decltype(w)::value>; }, n_steps,
+                                 policy_seed, returns, actions_out);
         });
     });
 }
@@ -2335,22 +2310,31 @@ int sbr_rollout_actions(sbr_env* e, int32_t n_steps, int32_t hold, const void* a
         dispatch(e, [&](auto c) {
             using C = decltype(c);
             using A = typename C::ActT;
-            const auto fn = fused_waves(e) == 1 ? k_rollout_tape<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_rollout_tape<A, C::OCI, C::SCH, 2>;
-            hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold,
-                               (const A*)actions, returns, rewards_out);
+            launch_fused<C::SCH>(e, e->n, stream, [](auto w) { return k_rollout_tape<A, C::OCI, C::SCH, decltype(w)::value>; }, n_steps,
+                                 hold, (const A*)actions, returns, rewards_out);
         });
     });
 }
 
+// The refusals every entry point with a fan-out shares.  Like the checks around them they overwrite `bad` where they fail: of all
+// the checks of an entry point the LAST failing one is reported.  word: what the upper 24 bits of the Philox stream word carry
+// where something is drawn per branch ("candidate", "branch"); NULL where nothing is, and the fan-out has no such limit.
+static void fanout_error(std::string& bad, const sbr_env* e, int32_t fanout, const char* word) {
+    if (fanout < 1) bad = "fanout must be >= 1";
+    else if (word && fanout > (1 << 24)) bad = std::string("fanout must be <= 2^24 (the ") + word + " is 24 bits of the Philox stream word)";
+    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+}
+static void best_error(std::string& bad, const double* returns, const int32_t* best_index, const double* best_return) {
+    if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
+}
 // What sbr_lookahead_actions and sbr_lookahead_actions_end have to say about the arguments they share; empty if they are valid.
 // Every check is evaluated, the LAST failing one is reported - all of them before anything is touched.
 static std::string lookahead_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions,
                                    const double* returns, const int32_t* best_index, const double* best_return) {
     std::string bad;
-    if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
+    best_error(bad, returns, best_index, best_return);
     if (!actions && n_steps > 0) bad = "NULL actions with n_steps > 0";
-    if (fanout < 1) bad = "fanout must be >= 1";
-    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+    fanout_error(bad, e, fanout, nullptr);
     if (hold < 1) bad = "hold must be >= 1";
     if (n_steps < 0) bad = "n_steps must be >= 0";
     if (!e) bad = "NULL env";
@@ -2362,9 +2346,11 @@ static std::string end_error(int32_t n_steps, const void* obs_end, const void* s
     if (!obs_end && !state_end && !done_end) return "obs_end, state_end and done_end are all NULL: call the entry point without _end";
     return "";
 }
-// k_branch_best behind a lookahead kernel on the same stream, or on its own (sbr_branch_best): one wavefront per env
+// k_branch_best behind a lookahead kernel on the same stream, where the caller wants a winner, or on its own (sbr_branch_best):
+// one wavefront per env
 static void launch_branch_best(const sbr_env* e, int32_t fanout, const double* values, int32_t* best_index, double* best_value,
                                void* stream) {
+    if (!best_index && !best_value) return;
     hipLaunchKernelGGL(k_branch_best, dim3((unsigned)((e->n + SBR_BLOCK / 64 - 1) / (SBR_BLOCK / 64))), dim3(SBR_BLOCK), 0,
                        (hipStream_t)stream, values, e->n, (uint32_t)fanout, best_index, best_value);
 }
@@ -2378,12 +2364,10 @@ int sbr_lookahead_actions(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fan
         dispatch(e, [&](auto c) {
             using C = decltype(c);
             using A = typename C::ActT;
-            // the register budget goes by the lanes of THIS launch, the branches, not by the handle's envs
-            const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_tape<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_tape<A, C::OCI, C::SCH, 2>;
-            hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
-                               (uint32_t)nb, (const A*)actions, returns, rewards_out);
+            launch_fused<C::SCH>(e, nb, stream, [](auto w) { return k_lookahead_tape<A, C::OCI, C::SCH, decltype(w)::value>; }, n_steps,
+                                 hold, (uint32_t)fanout, (uint32_t)nb, (const A*)actions, returns, rewards_out);
         });
-        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
+        launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
 }
 
@@ -2399,12 +2383,11 @@ int sbr_lookahead_actions_end(sbr_env* e, int32_t n_steps, int32_t hold, int32_t
         dispatch(e, [&](auto c) {
             using C = decltype(c);
             using A = typename C::ActT;
-            // the register budget goes by the branches, as in sbr_lookahead_actions
-            const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_tape_end<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_tape_end<A, C::OCI, C::SCH, 2>;
-            hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
-                               (uint32_t)nb, (const A*)actions, returns, rewards_out, obs_end, state_end, done_end);
+            launch_fused<C::SCH>(e, nb, stream, [](auto w) { return k_lookahead_tape_end<A, C::OCI, C::SCH, decltype(w)::value>; },
+                                 n_steps, hold, (uint32_t)fanout, (uint32_t)nb, (const A*)actions, returns, rewards_out, obs_end, state_end,
+                                 done_end);
         });
-        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
+        launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
 }
 
@@ -2412,8 +2395,7 @@ int sbr_branch_best(sbr_env* e, int32_t fanout, const double* values, int32_t* b
     std::string bad;
     if (!best_index && !best_value) bad = "best_index and best_value are both NULL";
     if (!values) bad = "NULL values";
-    if (fanout < 1) bad = "fanout must be >= 1";
-    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+    fanout_error(bad, e, fanout, nullptr);
     if (!e) bad = "NULL env";
     if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_branch_best: " + bad);
     return launched(e, [&] { launch_branch_best(e, fanout, values, best_index, best_value, stream); });
@@ -2422,9 +2404,7 @@ int sbr_branch_best(sbr_env* e, int32_t fanout, const double* values, int32_t* b
 // What sbr_lookahead_sampled and sbr_mppi_update have to say about a sampler and a fan-out; empty if they are valid.
 static std::string sampler_error(const sbr_env* e, const sbr_sampler* sm, int32_t fanout) {
     std::string bad;
-    if (fanout < 1) bad = "fanout must be >= 1";
-    else if (fanout > (1 << 24)) bad = "fanout must be <= 2^24 (the candidate is 24 bits of the Philox stream word)";
-    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+    fanout_error(bad, e, fanout, "candidate");
     if (!sm) return "NULL sampler";
     for (int c = 0; c < 2; ++c) {
         if (!(sm->sigma[c] >= 0) || !std::isfinite(sm->sigma[c])) bad = "sampler.sigma must be >= 0 and finite";
@@ -2438,7 +2418,7 @@ static std::string lookahead_sampled_error(const sbr_env* e, int32_t n_steps, in
                                            const sbr_sampler* sampler, const double* returns, const int32_t* best_index,
                                            const double* best_return) {
     std::string bad;
-    if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
+    best_error(bad, returns, best_index, best_return);
     if (!nominal && n_steps > 0) bad = "NULL nominal with n_steps > 0";
     const std::string sb = sampler_error(e, sampler, fanout);
     if (!sb.empty()) bad = sb;
@@ -2458,12 +2438,11 @@ int sbr_lookahead_sampled(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fan
         dispatch(e, [&](auto c) {
             using C = decltype(c);
             using A = typename C::ActT;
-            // the register budget goes by the branches, as in sbr_lookahead_actions
-            const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_sampled<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_sampled<A, C::OCI, C::SCH, 2>;
-            hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
-                               (uint32_t)nb, (const A*)nominal, *sampler, returns, rewards_out, (A*)actions_out);
+            launch_fused<C::SCH>(e, nb, stream, [](auto w) { return k_lookahead_sampled<A, C::OCI, C::SCH, decltype(w)::value>; },
+                                 n_steps, hold, (uint32_t)fanout, (uint32_t)nb, (const A*)nominal, *sampler, returns, rewards_out,
+                                 (A*)actions_out);
         });
-        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
+        launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
 }
 
@@ -2480,12 +2459,11 @@ int sbr_lookahead_sampled_end(sbr_env* e, int32_t n_steps, int32_t hold, int32_t
         dispatch(e, [&](auto c) {
             using C = decltype(c);
             using A = typename C::ActT;
-            const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_sampled_end<A, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_sampled_end<A, C::OCI, C::SCH, 2>;
-            hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
-                               (uint32_t)nb, (const A*)nominal, *sampler, returns, rewards_out, (A*)actions_out, obs_end, state_end,
-                               done_end);
+            launch_fused<C::SCH>(e, nb, stream, [](auto w) { return k_lookahead_sampled_end<A, C::OCI, C::SCH, decltype(w)::value>; },
+                                 n_steps, hold, (uint32_t)fanout, (uint32_t)nb, (const A*)nominal, *sampler, returns, rewards_out,
+                                 (A*)actions_out, obs_end, state_end, done_end);
         });
-        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
+        launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
 }
 
@@ -2575,9 +2553,8 @@ int sbr_rollout_policy(sbr_env* e, int32_t n_steps, int32_t hold, const sbr_poli
             using C = decltype(c);
             either(wide, [&](auto w64) {
                 constexpr int H = decltype(w64)::value ? 64 : 32;
-                const auto fn = fused_waves(e) == 1 ? k_rollout_policy<H, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_rollout_policy<H, C::OCI, C::SCH, 2>;
-                hipLaunchKernelGGL(fn, grid_for(e->n), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold,
-                                   policy->params, pl, obs, returns, actions_out, rewards_out);
+                launch_fused<C::SCH>(e, e->n, stream, [](auto w) { return k_rollout_policy<H, C::OCI, C::SCH, decltype(w)::value>; },
+                                     n_steps, hold, policy->params, pl, obs, returns, actions_out, rewards_out);
             });
         });
     });
@@ -2593,11 +2570,9 @@ int sbr_lookahead_policy(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fano
     else if (n_steps == 0 && (obs_end || state_end || done_end))
         bad = "n_steps = 0 has no end state to report that the handle does not already hold";
     if (hold < 1) bad = "hold must be >= 1";
-    if (fanout < 1) bad = "fanout must be >= 1";
-    else if (fanout > (1 << 24)) bad = "fanout must be <= 2^24 (the branch is 24 bits of the Philox stream word)";
-    else if (e && e->n * (int64_t)fanout >= (int64_t)1 << 31) bad = "num_envs * fanout must stay below 2^31 branches";
+    fanout_error(bad, e, fanout, "branch");
     if (keep_mean != 0 && keep_mean != 1) bad = "keep_mean must be 0 or 1";
-    if ((best_index || best_return) && !returns) bad = "best_index / best_return are reduced from returns: give returns with them";
+    best_error(bad, returns, best_index, best_return);
     if (!obs) bad = "NULL obs";
     const std::string pb = policy_error(e, policy);
     if (!pb.empty()) bad = pb;
@@ -2610,14 +2585,12 @@ int sbr_lookahead_policy(sbr_env* e, int32_t n_steps, int32_t hold, int32_t fano
             using C = decltype(c);
             either(wide, [&](auto w64) {
                 constexpr int H = decltype(w64)::value ? 64 : 32;
-                // the register budget goes by the branches, as in sbr_lookahead_actions
-                const auto fn = fused_waves_for(e, nb) == 1 ? k_lookahead_policy<H, C::OCI, C::SCH, kFusedOneWave<C::SCH>> : k_lookahead_policy<H, C::OCI, C::SCH, 2>;
-                hipLaunchKernelGGL(fn, grid_for(nb), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, n_steps, hold, (uint32_t)fanout,
-                                   (uint32_t)nb, policy->params, pl, keep_mean, obs, returns, rewards_out, actions_out, obs_end, state_end,
-                                   done_end);
+                launch_fused<C::SCH>(e, nb, stream, [](auto w) { return k_lookahead_policy<H, C::OCI, C::SCH, decltype(w)::value>; },
+                                     n_steps, hold, (uint32_t)fanout, (uint32_t)nb, policy->params, pl, keep_mean, obs, returns, rewards_out,
+                                     actions_out, obs_end, state_end, done_end);
             });
         });
-        if (best_index || best_return) launch_branch_best(e, fanout, returns, best_index, best_return, stream);
+        launch_branch_best(e, fanout, returns, best_index, best_return, stream);
     });
 }
 
