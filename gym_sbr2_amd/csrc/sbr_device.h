@@ -685,7 +685,7 @@ SBR_DEV int sbr_status_bits(const SbrPar& p, const double (&x)[SBR_NX]) {
 struct SbrNoTrace { SBR_DEV void pid(int, double, double, double) const {} };
 // SCH: cfg.scheme at compile time (a kernel instantiation per scheme: the scheme-1 kernels carry no RK4 loop for the intervals).
 // PA: where the constants come from AFTER the step loop (SbrParKeep: the caller's `p`; k_step reads them again, see SbrParAgain
-// in sbr_amd.hip).  Returns the set to go on with.
+// in sbr_core.hip).  Returns the set to go on with.
 struct SbrParKeep { SBR_DEV const SbrPar& again(const SbrPar& p) const { return p; } };
 template <int SCH, typename X6, typename TR, typename PA>
 SBR_DEV const SbrPar& sbr_interval(const SbrPar& p, SbrCtl& c, double (&x)[SBR_NX], X6& xs6, bool aerobic, const TR& tr, const PA& pa) {

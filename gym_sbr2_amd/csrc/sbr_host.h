@@ -1,0 +1,125 @@
+// sbr_host.h - the host side every translation unit of libsbr_amd.so shares: the handle, error reporting, the frame of an
+// entry point, the launch shapes and the one place that turns run-time choices into template arguments.
+#pragma once
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <type_traits>
+
+#include "sbr_kernels.h"
+
+#define SBR_INTERNAL __attribute__((visibility("hidden")))     // shared between the units, not part of the C ABI
+
+struct sbr_env {
+    int64_t n = 0;
+    int device = 0;
+    int64_t first_env_id = 0;
+    sbr_config cfg;
+    SbrPar par;
+    SbrBuf buf{};
+    double* tables = nullptr;     // [2][8][14][48] on the device
+    int64_t one_wave_envs = 65536; // lanes of one wave per SIMD on this device: CUs x 4 SIMDs x 64 (MI355X: 256 CUs)
+    bool have_tables = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::string err;
+};
+
+// Defined once, in sbr_core.hip, next to the calling thread's error text it writes when there is no handle (sbr_last_error(NULL)):
+// a copy per unit would each keep a text of its own.
+SBR_INTERNAL int fail(sbr_env* e, int code, const std::string& msg);
+// A failed HIP call.  Only sbr_create passes no handle (the one it is building is not the caller's yet), and only there does
+// running out of device memory have a code of its own.
+static inline int hip_fail(sbr_env* e, hipError_t s, const char* call) {
+    return fail(e, !e && s == hipErrorOutOfMemory ? SBR_ERR_ALLOC : SBR_ERR_HIP, std::string(call) + ": " + hipGetErrorString(s));
+}
+#define HIP_TRY(e, call)                                          \
+    do {                                                          \
+        hipError_t _s = (call);                                   \
+        if (_s != hipSuccess) return hip_fail(e, _s, #call);      \
+    } while (0)
+
+static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + SBR_BLOCK - 1) / SBR_BLOCK)); }
+
+// Entry points run on the handle's device and leave the caller's current device as they found it (a process may drive
+// several GPUs, and torch tracks the current device itself).
+struct DeviceGuard {
+    int prev = -1;
+    hipError_t status = hipSuccess;
+    explicit DeviceGuard(int device) {
+        int cur = -1;
+        status = hipGetDevice(&cur);
+        if (status == hipSuccess && cur != device) { status = hipSetDevice(device); prev = cur; }
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+#define ON_DEVICE(e)                      \
+    DeviceGuard _guard((e)->device);      \
+    HIP_TRY(e, _guard.status)
+// The frame of an entry point that only launches kernels, behind its own argument check: launch() runs on the handle's device
+// and the launch status is collected once behind it.  (Entry points that copy or wait check each call where it is made:
+// ON_DEVICE, then HIP_TRY per call.)
+template <typename Launch> static int launched(sbr_env* e, Launch&& launch) {
+    ON_DEVICE(e);
+    launch();
+    HIP_TRY(e, hipGetLastError());
+    return SBR_OK;
+}
+
+// Launch shapes.  Each decision is taken once, here: the launch sites and sbr_query both read these functions.
+#define SBR_SMALL_BATCH 49152       // up to this many envs k_step runs in 64-thread workgroups (measured: profiles/r02_ab_block.log)
+static inline int step_block(const sbr_env* e) { return e->n <= SBR_SMALL_BATCH ? 64 : 256; }
+// A launch with more wavefronts than the device has SIMDs (MI355X: 1024 SIMDs x 64 lanes = 65536 envs; a partitioned device has
+// fewer) runs the two-waves-per-SIMD build of the scheme-1 k_step.
+static inline int64_t step_two_waves_above(const sbr_env* e) { return e->one_wave_envs > SBR_SMALL_BATCH ? e->one_wave_envs : SBR_SMALL_BATCH; }
+static inline int step_waves(const sbr_env* e) { return e->cfg.scheme == 1 && e->n > step_two_waves_above(e) ? 2 : 1; }
+// up to 1.5 waves per SIMD (MI355X: 98304 envs) the fused scheme-1 kernels (k_rollout, k_cycle) run their uncapped-register build
+static inline int64_t fused_one_wave_max(const sbr_env* e) { return e->one_wave_envs + e->one_wave_envs / 2; }
+static inline int fused_waves(const sbr_env* e) { return e->cfg.scheme == 1 && e->n <= fused_one_wave_max(e) ? 1 : 2; }
+// the same decision for a launch of `lanes` lanes that are not the handle's envs (sbr_lookahead_actions: one lane per branch)
+static inline int fused_waves_for(const sbr_env* e, int64_t lanes) { return e->cfg.scheme == 1 && lanes <= fused_one_wave_max(e) ? 1 : 2; }
+// more waves than SIMDs: k_reset in 512-thread workgroups, two waves per SIMD
+static inline int reset_block(const sbr_env* e) { return e->n > e->one_wave_envs ? 512 : SBR_RESET_BLOCK; }
+
+// The handle's run-time choices as template arguments.  This is the only place that turns one into the other: f is called with
+// a Choice that names the output and action types, whether the reward is the operating cost (reward_kind 2) and the scheme.
+// A launch site names its kernel once, with the members of the Choice it needs.  Which WAVES builds of a kernel exist stays
+// with the launch site: a kernel is instantiated wherever its name is spelled, taken or not.
+template <typename OutT_, typename ActT_, bool OCI_, int SCH_>
+struct Choice {
+    using OutT = OutT_;
+    using ActT = ActT_;
+    static constexpr bool OCI = OCI_;
+    static constexpr int SCH = SCH_;
+};
+template <typename F> static void either(bool c, F&& f) { if (c) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> static void dispatch(const sbr_env* e, F&& f) {
+    either(e->cfg.out_f64, [&](auto o64) { either(e->cfg.act_f64, [&](auto a64) {
+        either(e->cfg.reward_kind == 2, [&](auto oci) { either(e->cfg.scheme == 1, [&](auto b5) {
+            f(Choice<std::conditional_t<decltype(o64)::value, double, float>, std::conditional_t<decltype(a64)::value, double, float>,
+                     decltype(oci)::value, decltype(b5)::value ? 1 : 0>{});
+        }); });
+    }); });
+}
+
+// the fused kernels (k_cycle, k_rollout and the kernels behind it): scheme 0 has no one-wave build (fused_waves is 2 for it)
+template <int SCH> constexpr int kFusedOneWave = SCH == 1 ? 1 : 2;
+// The launch of a fused kernel over `lanes` lanes: the handle's envs, or the branches of a lookahead - the register budget goes by
+// the lanes of THE launch.  kernel(w) names the build for decltype(w)::value waves per SIMD; e->par and e->buf lead its arguments.
+template <int SCH, typename Kernel, typename... Args>
+static void launch_fused(const sbr_env* e, int64_t lanes, void* stream, Kernel&& kernel, Args... args) {
+    const auto fn = fused_waves_for(e, lanes) == 1 ? kernel(std::integral_constant<int, kFusedOneWave<SCH>>{})
+                                                   : kernel(std::integral_constant<int, 2>{});
+    hipLaunchKernelGGL(fn, grid_for(lanes), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, args...);
+}
+
+// Argument checks that several families share, and the one kernel two of them launch without owning it: defined in
+// sbr_tape.hip, which owns k_branch_best.
+SBR_INTERNAL void fanout_error(std::string& bad, const sbr_env* e, int32_t fanout, const char* word);
+SBR_INTERNAL void best_error(std::string& bad, const double* returns, const int32_t* best_index, const double* best_return);
+SBR_INTERNAL std::string end_error(int32_t n_steps, const void* obs_end, const void* state_end, const void* done_end);
+SBR_INTERNAL void launch_branch_best(const sbr_env* e, int32_t fanout, const double* values, int32_t* best_index, double* best_value,
+                                     void* stream);

@@ -23,7 +23,7 @@ META = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spil
 
 
 def kernels(asm):
-    return re.findall(r"^\s+\.name:\s+(\S+)\n", asm[asm.index("amdhsa.kernels:"):], re.M)
+    return isa.kernel_names(asm)      # over every translation unit's metadata where the text is several units' one behind the other
 
 
 def base_name(symbol):
@@ -32,11 +32,15 @@ def base_name(symbol):
 
 
 def text_key(text):
-    out = []
+    """Instructions and local labels of a kernel with what only counts through the translation unit taken out of the label
+    names: the function number of .LBB<f>_<n>, and the unit-wide counter of the long-branch labels .Lpost_getpc<c>, which are
+    numbered again in the order the kernel first names them."""
+    out, getpc = [], {}
     for raw in text.split("\n"):
         l = raw.split(";")[0].strip()
         if l and (l.endswith(":") or not l.startswith(".")):
-            out.append(re.sub(r"\.LBB\d+_", ".LBB_", l))
+            l = re.sub(r"\.LBB\d+_", ".LBB_", l)
+            out.append(re.sub(r"\.Lpost_getpc(\d+)", lambda m: ".Lpost_getpc#%d" % getpc.setdefault(m.group(1), len(getpc)), l))
     return out
 
 

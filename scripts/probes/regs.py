@@ -2,7 +2,6 @@
    python scripts/probes/regs.py "-DSBR_STAMPS" [symbol-substring ...]"""
 import os
 import re
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,10 +10,7 @@ from gym_sbr2_amd import build as B
 
 flags = sys.argv[1].split() if len(sys.argv) > 1 else []
 want = sys.argv[2:] or ["k_step"]
-out = os.path.join(ROOT, "build", "regs_probe.s")
-base = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
-subprocess.check_call([B.hipcc()] + base + flags + ["-S", "--cuda-device-only", "-o", out, B.SRC], stderr=subprocess.DEVNULL)
-asm = open(out).read()
+asm = "".join(B.compile_library(flags))
 for ent in re.split(r"\n  - \.agpr_count:", asm)[1:]:
     ent = ".agpr_count:" + ent
     name = re.search(r"\.name:\s+(\S+)", ent).group(1)

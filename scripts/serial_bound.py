@@ -22,8 +22,7 @@ from gym_sbr2_amd import build as B  # noqa: E402
 tag = sys.argv[1] if len(sys.argv) > 1 else "r05"
 stamps = os.path.join(ROOT, "build", "libsbr_amd_stamps.so")
 os.makedirs(os.path.dirname(stamps), exist_ok=True)
-flags = [f for f in B.FLAGS] + ["-DSBR_STAMPS"]
-subprocess.check_call([B.hipcc()] + flags + ["-o", stamps, B.SRC])          # always rebuilt: the same sources as the library
+B.compile_library(["-DSBR_STAMPS"], out=stamps)          # always rebuilt: the same sources as the library
 env = dict(os.environ, SBR_AMD_LIB=stamps, SBR_AMD_ALLOW_ABI_MISMATCH="0")
 tl = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "probes", "step_timeline.py"), "65536"], env=env,
                     capture_output=True, text=True).stdout

@@ -7,8 +7,6 @@ import functools
 import os
 import re
 import shutil
-import subprocess
-import tempfile
 
 import pytest
 
@@ -42,17 +40,26 @@ K_POL = {(h, sch, wv): "_Z16k_rollout_policyILi%dELb0ELi%dELi%dEE" % (h, sch, wv
 
 
 @functools.lru_cache(maxsize=None)
-def library_asm():
-    """The assembly text of the library's source under the library's own flags.  Minutes of hipcc, so once per process: the
-    module-scoped `asm` fixtures of the four test files all return this one string."""
+def unit_asms():
+    """{unit's file name: its assembly text} under the library's own flags, in the order of the build's SOURCES.  Minutes of
+    hipcc (the units side by side), so once per process."""
     if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("hipcc not available")
-    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC")]
-    with tempfile.TemporaryDirectory(prefix="isa") as tmp:
-        out = os.path.join(tmp, "sbr_amd.s")
-        subprocess.check_call([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", out, B.SRC], stderr=subprocess.DEVNULL)
-        with open(out) as f:
-            return f.read()
+    return dict(zip(map(os.path.basename, B.SOURCES), B.compile_library()))
+
+
+@functools.lru_cache(maxsize=None)
+def library_asm():
+    """The assembly text of the whole library: the units' texts one behind the other.  The module-scoped `asm` fixtures of the
+    four test files all return this one string."""
+    return "".join(unit_asms().values())
+
+
+def kernel_names(asm):
+    """The symbols of the kernels in the code objects' metadata: every `.name:` of every amdhsa.kernels list of the text (one
+    list per translation unit; `.name:` one level deeper names a kernel ARGUMENT and does not match)."""
+    assert "amdhsa.kernels:" in asm
+    return re.findall(r"^    \.name:\s+(\S+)\n", asm, re.M)
 
 
 def kernel_text(asm, symbol):
@@ -108,12 +115,16 @@ def f64_mix(ins):
 
 def meta(asm, symbol, key):
     """A field of the kernel's entry in the code object's metadata (amdhsa.kernels).  The entries are YAML maps whose keys are
-    sorted, so some precede `.name` and some follow it: take the whole entry (it starts at `  - .agpr_count:`)."""
-    for blk in re.split(r"\n  - (?=\.agpr_count:)", asm[asm.index("amdhsa.kernels:"):]):
-        if re.search(r"\.name:\s+%s\S*\n" % re.escape(symbol), blk):
-            m = re.search(r"^\s+\.%s:\s+(\d+)" % key, "\n    " + blk, re.M)
-            assert m, (symbol, key)
-            return int(m.group(1))
+    sorted, so some precede `.name` and some follow it: take the whole entry (it starts at `  - .agpr_count:`).  The text holds
+    one amdhsa.kernels list per translation unit, each closed by its amdhsa.target line."""
+    lists = re.findall(r"^amdhsa\.kernels:\n(.*?)^amdhsa\.target:", asm, re.S | re.M)
+    assert lists, "no kernel metadata in the text"
+    for lst in lists:
+        for blk in re.split(r"\n  - (?=\.agpr_count:)", "\n" + lst)[1:]:
+            if re.search(r"\.name:\s+%s\S*\n" % re.escape(symbol), blk):
+                m = re.search(r"^\s+\.%s:\s+(\d+)" % key, "\n    " + blk, re.M)
+                assert m, (symbol, key)
+                return int(m.group(1))
     raise AssertionError((symbol, "not in the metadata"))
 
 

@@ -6,8 +6,8 @@ import re
 import pytest
 from conftest import ROOT
 from isa import (K_CYCLE, K_CYCLE_RESET, K_CYCLE_RK4, K_RESET, K_RESET_CARRY, K_RESET_WIDE, K_ROLLOUT, K_ROLLOUT_2W, K_ROLLOUT_RK4,
-                 K_STEP, K_STEP_2W, K_STEP_RK4, K_STEP_SMALL, b5_steps, f64_mix, flop_counts, instructions, kernel_text, library_asm,
-                 meta, rk4_loops)
+                 K_STEP, K_STEP_2W, K_STEP_RK4, K_STEP_SMALL, b5_steps, f64_mix, flop_counts, instructions, kernel_names, kernel_text, library_asm,
+                 meta, rk4_loops, unit_asms)
 
 from gym_sbr2_amd import build as B
 
@@ -67,6 +67,30 @@ def test_butcher5_step_loops(asm):
     rk4 = lambda k: rk4_loops(kernel_text(asm, k))   # noqa: E731
     assert len(rk4(K_STEP)) == 0 and len(rk4(K_ROLLOUT)) == 0 and len(rk4(K_STEP_RK4)) >= 2 and len(rk4(K_ROLLOUT_RK4)) >= 2
     assert len(instructions(kernel_text(asm, K_STEP))) < 0.8 * 11200      # 7 614 instructions; 11 142 with both schemes in one kernel
+
+
+def test_every_kernel_has_exactly_one_owning_translation_unit(asm):
+    """The library is several translation units linked without relocatable device code: a kernel named by launch sites in two of
+    them would be compiled twice and exist as two copies in two code objects.  Every kernel symbol of the metadata is in ONE unit's
+    assembly, and the units together hold the kernels of the whole text."""
+    owners = {}
+    for unit, text in unit_asms().items():
+        names = kernel_names(text)
+        assert names and len(set(names)) == len(names), unit
+        for n in names:
+            owners.setdefault(n, []).append(unit)
+    shared = {n: u for n, u in owners.items() if len(u) != 1}
+    assert not shared, shared
+    assert sorted(owners) == sorted(kernel_names(asm)) and any(n.startswith(K_STEP) for n in owners)
+
+
+def test_the_one_file_source_names_the_units_of_the_build():
+    """build.SRC is the library as one translation unit for tools that take a single file: its #include lines are SOURCES, in
+    order, and nothing else is in it."""
+    import os
+    with open(B.SRC) as f:
+        code = [l.strip() for l in f if l.strip() and not l.lstrip().startswith("//")]
+    assert code == ['#include "%s"' % os.path.basename(s) for s in B.SOURCES]
 
 
 def test_fused_multiply_adds_are_the_ones_the_source_spells_out():

@@ -82,6 +82,16 @@ assert lib.sbr_destroy(None) == 0 and lib.sbr_num_envs(None) == 0
 for fn, args in (("sbr_step", (None,) * 7), ("sbr_reset", (None, C.c_uint64(0)) + (None,) * 6), ("sbr_set_trace", (None, None, C.c_int64(0), C.c_int64(0), 34)),
                  ("sbr_rollout", (None, 1, C.c_uint64(0), None, None, None)), ("sbr_get_state", (None,) * 4), ("sbr_synchronize", (None, None))):
     assert getattr(lib, fn)(*args) != 0, fn
+# the calling thread's error text is ONE variable of the library (sbr_core.hip), whichever translation unit's entry point reports
+# through it: a refusal without a handle from each of the other units, read back through sbr_last_error(NULL) of the core unit
+# (the texts as the single-file library gave them)
+for fn, args, text in (("sbr_rollout", (None, 1, C.c_uint64(0), None, None, None), b"sbr_rollout: bad argument"),
+                       ("sbr_rollout_actions", (None, 1, 1, None, None, None, None), b"sbr_rollout_actions: need n_steps >= 0, hold >= 1 and an action tape"),
+                       ("sbr_lookahead_sampled", (None, 1, 1, 2) + (None,) * 8, b"sbr_lookahead_sampled: NULL env"),
+                       ("sbr_rollout_policy", (None, 1, 1) + (None,) * 6, b"sbr_rollout_policy: NULL policy"),
+                       ("sbr_lookahead_policy", (None, 1, 1, 2, None, 0) + (None,) * 10, b"sbr_lookahead_policy: NULL policy"),
+                       ("sbr_step", (None,) * 7, b"sbr_step: NULL env or action")):
+    assert getattr(lib, fn)(*args) == -1 and lib.sbr_last_error(None) == text, (fn, lib.sbr_last_error(None))
 print("ok")
 '''
 
@@ -94,8 +104,7 @@ def test_host_half_of_the_library_under_ubsan_without_a_device(tmp_path):
     behaviour kills the child with SIGILL).  The device code is compiled as always - the sanitizer does not exist for amdgcn."""
     from gym_sbr2_amd import build as B
     lib = str(tmp_path / "libsbr_amd_ubsan.so")
-    flags = [f for f in B.FLAGS if f != "-O3"] + ["-O1", "-fsanitize=undefined", "-fsanitize-trap=undefined"]
-    subprocess.check_call([B.hipcc()] + flags + ["-o", lib, B.SRC], stderr=subprocess.DEVNULL)
+    B.compile_library(["-O1", "-fsanitize=undefined", "-fsanitize-trap=undefined"], out=lib)      # -O1 behind FLAGS' -O3: the later one holds
     env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
     p = subprocess.run([sys.executable, "-c", HOST_CHILD % ROOT, lib], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert p.returncode == 0 and p.stdout.strip().endswith("ok"), (p.returncode, p.stderr[-2000:])
