@@ -26,6 +26,9 @@ def __getattr__(name):          # torch is imported only when the env classes ar
     if name == "SbrOSVec":
         from .vec_env import SbrOSVec
         return SbrOSVec
+    if name == "PolicyCollection":
+        from .vec_env import PolicyCollection
+        return PolicyCollection
     if name == "SbrOS":
         from .envs import SbrOS
         return SbrOS

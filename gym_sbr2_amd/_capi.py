@@ -27,6 +27,7 @@ PLAN_SLAVED = 128    # SBR_PLAN_SLAVED: C_PLAN / TR_PLAN = Butcher-5 step count 
 (Q_ONE_WAVE_ENVS, Q_STEP_SMALL_BATCH_ENVS, Q_STEP_BLOCK, Q_STEP_WAVES, Q_STEP_TWO_WAVES_ABOVE_ENVS, Q_FUSED_ONE_WAVE_MAX_ENVS,
  Q_ROLLOUT_WAVES, Q_RESET_BLOCK, Q_SCHEME) = range(9)
 ST_NEGATIVE, ST_NEAR_POLE, ST_NONFINITE = 1, 2, 4     # SBR_ST_* bits of the status row
+DF_TAKEN, DF_ENDED = 1, 2     # SBR_DF_* bits of sbr_collect_policy's flags_out: the decision was taken / its transition is terminal
 # cfg.reward_kind: module_reward_EQIOCI.py (SBROS-v1) / module_reward_continuous_G2ANET.py / module_reward_continuous.py
 REWARD_KINDS = {"eqi_oci": 0, "g2anet": 1, "oci": 2}
 
@@ -94,6 +95,7 @@ SYMBOLS = {
     "sbr_mppi_update": (C.c_int, [_VP, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, C.c_double, _I32, _VP, _VP, _VP]),
     "sbr_policy_param_count": (_I64, [_I32, _I32]),
     "sbr_rollout_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP]),
+    "sbr_collect_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_policy": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(SbrPolicy), _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                        _VP]),
     "sbr_reduce_stats": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),

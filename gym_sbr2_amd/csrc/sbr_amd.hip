@@ -6,3 +6,4 @@
 #include "sbr_sampled.hip"
 #include "sbr_policy.hip"
 #include "sbr_policy_lookahead.hip"
+#include "sbr_policy_collect.hip"

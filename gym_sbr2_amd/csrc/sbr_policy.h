@@ -1,5 +1,6 @@
-// sbr_policy.h - what the two units of the policy family share (sbr_policy.hip, sbr_policy_lookahead.hip): the caller's MLP as
-// the kernels evaluate it, and the host's checks of an sbr_policy.
+// sbr_policy.h - what the three units of the policy family share (sbr_policy.hip, sbr_policy_lookahead.hip,
+// sbr_policy_collect.hip): the caller's MLP as the kernels evaluate it, the noise of a decision, and the host's checks of an
+// sbr_policy.
 #pragma once
 #include "sbr_host.h"
 
@@ -77,8 +78,20 @@ SBR_DEV void sbr_mlp(const SbrPolicyDev& pl, const float* __restrict__ w, const 
     }
     sbr_mlp_layer<H, 2, 2>(w, h, y);
 }
+// exploration noise of a decision (k_rollout_policy, k_collect_policy): one Box-Muller pair of Philox stream 3, subsequence =
+// global env id, counter = the env's calls since reset (sbr_normal_pair's construction; streams 0 - 2 are the influent, the
+// random policy and the scenario draw)
+SBR_DEV void sbr_policy_noise(uint64_t seed, uint64_t env_id, uint32_t call, double& z0, double& z1) {
+    uint32_t c[4] = {call, 3u, (uint32_t)env_id, (uint32_t)(env_id >> 32)};
+    sbr_philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const double u1 = sbr_u53(c[0], c[1]), u2 = sbr_u53(c[2], c[3]);
+    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;
+    double sn, cs;
+    sincos(ang, &sn, &cs);
+    z0 = rad * cs; z1 = rad * sn;
+}
 
-// What sbr_rollout_policy and sbr_lookahead_policy have to say about a policy (empty if it is valid), and a validated sbr_policy
+// What sbr_rollout_policy, sbr_collect_policy and sbr_lookahead_policy have to say about a policy (empty if it is valid), and a validated sbr_policy
 // as the kernels take it: defined in sbr_policy.hip.
 SBR_INTERNAL std::string policy_error(const sbr_env* e, const sbr_policy* policy);
 SBR_INTERNAL SbrPolicyDev policy_dev(const sbr_policy* policy);

@@ -9,18 +9,7 @@
 // observation, evaluated in the lane that holds the plant.  The loop body is the tape kernel's - sbr_run_intervals,
 // sbr_finish_step with the register history, sbr_terminal once after the loop - so an env fed this kernel's own actions_out as a
 // tape ends with the same bits.
-// The net: sbr_policy.h.
-// exploration noise of a decision: one Box-Muller pair of Philox stream 3, subsequence = global env id, counter = the env's
-// calls since reset (sbr_normal_pair's construction; streams 0 - 2 are the influent, the random policy and the scenario draw)
-SBR_DEV void sbr_policy_noise(uint64_t seed, uint64_t env_id, uint32_t call, double& z0, double& z1) {
-    uint32_t c[4] = {call, 3u, (uint32_t)env_id, (uint32_t)(env_id >> 32)};
-    sbr_philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const double u1 = sbr_u53(c[0], c[1]), u2 = sbr_u53(c[2], c[3]);
-    const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;
-    double sn, cs;
-    sincos(ang, &sn, &cs);
-    z0 = rad * cs; z1 = rad * sn;
-}
+// The net and the exploration noise of a decision (sbr_policy_noise): sbr_policy.h.
 // obs [N][18] float32, in and out: on entry the observation in force, on exit the current one of every env that is not done
 // (a done env's row is left alone).  In between the observation is never stored: before a decision it is formed in registers
 // from the plant, the interval's start values (x6) and the running time, exactly as k_step forms the row it returns.

@@ -51,6 +51,9 @@ class SbrEnv2Vec(SbrOSVec):
     def lookahead_policy(self, *a, **k):
         raise NotImplementedError("the closed-loop lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 
+    def collect_policy(self, *a, **k):
+        raise NotImplementedError("the fused policy collector belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+
     def branch_best(self, *a, **k):
         raise NotImplementedError("the winner of a lookahead's branches belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 

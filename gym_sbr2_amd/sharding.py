@@ -148,6 +148,12 @@ class ShardedSbrOS:
         return self.env.rollout_policy(policy, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed,
                                        return_actions=return_actions, return_rewards=return_rewards)
 
+    def collect_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0):
+        """SbrOSVec.collect_policy for this rank's block (`obs` [n_local, 18] and every field of the result are the rank's own
+        slices).  `policy` is the WHOLE population on every rank, as in rollout_policy, and the noise is keyed by the global env
+        id, so the result does not depend on the world size."""
+        return self.env.collect_policy(policy, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed)
+
     def lookahead_policy(self, policy, fanout, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, keep_mean=False,
                          return_rewards=False, return_best=False, return_actions=False, return_end=False):
         """SbrOSVec.lookahead_policy for this rank's block (`obs` [n_local, 18] and every result are the rank's own slices).

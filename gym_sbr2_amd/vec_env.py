@@ -4,6 +4,7 @@
 PyTorch is used for device memory and streams only; every number comes out of libsbr_amd.so
 (HIP kernels) through the C ABI of include/sbr_amd.h.  There is no CPU path.
 """
+import collections
 import ctypes as C
 import os
 
@@ -29,6 +30,21 @@ def _ptr(t):
 def _one_or_all(out):
     """What a method with optional results returns: the tuple, or its only member."""
     return out if len(out) > 1 else out[0]
+
+
+class PolicyCollection(collections.namedtuple("PolicyCollection", "obs actions rewards flags returns last_obs")):
+    """What SbrOSVec.collect_policy returns (the shapes are given there)."""
+    __slots__ = ()
+
+    @property
+    def taken(self):
+        """[rows, N] bool: the decision was taken (the env's episode had not ended before it)."""
+        return (self.flags & _capi.DF_TAKEN) != 0
+
+    @property
+    def ended(self):
+        """[rows, N] bool: the env's episode ended during one of the decision's calls - the transition is terminal."""
+        return (self.flags & _capi.DF_ENDED) != 0
 
 
 # the handle of torch's current stream on a device: torch's own fast accessor (an int, no Stream object) where it exists
@@ -393,30 +409,67 @@ class SbrOSVec:
         float32 (exactly the values that were integrated; 0 where an env had finished) and the reward of every call
         [n_steps, N] float64."""
         n_steps, hold = int(n_steps), int(hold)
-        if hold < 1:
-            raise ValueError("hold must be >= 1")
-        if n_steps < 0:
-            raise ValueError("n_steps must be >= 0")
         n = self.num_envs
-        own = obs is None
-        o = self.obs if own else obs
-        if own and o.dtype != torch.float32:
-            o = o.to(torch.float32)
-        if not (isinstance(o, torch.Tensor) and o.dtype == torch.float32 and o.device == self.device and o.is_contiguous()
-                and tuple(o.shape) == (n, _capi.NOBS)):
-            raise ValueError("obs must be a contiguous float32 tensor of shape [N,%d] on %s (it is updated in place)"
-                             % (_capi.NOBS, self.device))
-        pol = policy.c_struct(self.device, noise_std=noise_std, noise_seed=noise_seed)
-        self._keep_p = (policy, pol, o)
+        o, pol = self._policy_inputs(policy, n_steps, hold, obs, noise_std, noise_seed)
         ret = torch.empty((n,), dtype=torch.float64, device=self.device)
         acts = torch.empty((-(-n_steps // hold), n, 2), dtype=torch.float32, device=self.device) if return_actions else None
         rew = torch.empty((n_steps, n), dtype=torch.float64, device=self.device) if return_rewards else None
         _capi.check(self.lib.sbr_rollout_policy(self._h, n_steps, hold, C.byref(pol), _ptr(o), _ptr(ret), _ptr(acts), _ptr(rew),
                                                 self._stream()), self._h)
-        if own and o is not self.obs:        # a float64 handle: the rows of the envs that are not done come back, the others stay
+        self._policy_obs_back(obs, o)
+        return _one_or_all((ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ()))
+
+    def _policy_inputs(self, policy, n_steps, hold, obs, noise_std, noise_seed):
+        """What rollout_policy and collect_policy hand the library: the in/out observation (obs=None: self.obs, as float32) and
+        the sbr_policy struct."""
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        if n_steps < 0:
+            raise ValueError("n_steps must be >= 0")
+        own = obs is None
+        o = self.obs if own else obs
+        if own and o.dtype != torch.float32:
+            o = o.to(torch.float32)
+        if not (isinstance(o, torch.Tensor) and o.dtype == torch.float32 and o.device == self.device and o.is_contiguous()
+                and tuple(o.shape) == (self.num_envs, _capi.NOBS)):
+            raise ValueError("obs must be a contiguous float32 tensor of shape [N,%d] on %s (it is updated in place)"
+                             % (_capi.NOBS, self.device))
+        pol = policy.c_struct(self.device, noise_std=noise_std, noise_seed=noise_seed)
+        self._keep_p = (policy, pol, o)
+        return o, pol
+
+    def _policy_obs_back(self, obs, o):
+        if obs is None and o is not self.obs:   # a float64 handle: the rows of the envs that are not done come back, the others stay
             live = self.ctrl_row(_capi.C_DONE) == 0
             self.obs.copy_(torch.where(live[:, None], o.to(self.obs.dtype), self.obs))
-        return _one_or_all((ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ()))
+
+    def collect_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0):
+        """rollout_policy as a COLLECTOR, one launch (sbr_collect_policy): the same calls with the same bits in the handle, `obs`
+        and every shared result, plus what a gradient-based learner needs of every decision d (rows = ceil(n_steps/hold) of
+        them).  `policy`, `hold`, `obs` (obs=None: self.obs), noise_std and noise_seed are rollout_policy's.  Returns a
+        PolicyCollection:
+          obs      [rows, N, 18] float32  the observation the net was applied to at decision d (zeros where the env had finished)
+          actions  [rows, N, 2]  float32  the decisions exactly as they were integrated (0 where the env had finished)
+          rewards  [n_steps, N]  float64  the reward of every call
+          flags    [rows, N]     uint8    _capi.DF_TAKEN | _capi.DF_ENDED; .taken and .ended are the two bits as bool tensors
+          returns  [N]           float64  the sum of this launch's rewards
+          last_obs [N, 18]       float32  the in/out observation after the launch, for bootstrapping
+        The action mean of a decision is the net applied to its row of `obs`; a learner recomputes it under autograd."""
+        n_steps, hold = int(n_steps), int(hold)
+        n, dev = self.num_envs, self.device
+        o, pol = self._policy_inputs(policy, n_steps, hold, obs, noise_std, noise_seed)
+        rows = -(-n_steps // hold)
+        ret = torch.empty((n,), dtype=torch.float64, device=dev)
+        acts = torch.empty((rows, n, 2), dtype=torch.float32, device=dev)
+        rew = torch.empty((n_steps, n), dtype=torch.float64, device=dev)
+        obs_out = torch.empty((rows, n, _capi.NOBS), dtype=torch.float32, device=dev)
+        # (a tensor without elements reports a NULL pointer, and the library refuses the call without either per-decision output:
+        # with n_steps = 0 the flags are the zero rows of a one-row buffer, which is not written)
+        flags = torch.empty((max(rows, 1), n), dtype=torch.uint8, device=dev)
+        _capi.check(self.lib.sbr_collect_policy(self._h, n_steps, hold, C.byref(pol), _ptr(o), _ptr(ret), _ptr(acts), _ptr(rew),
+                                                _ptr(obs_out), _ptr(flags), self._stream()), self._h)
+        self._policy_obs_back(obs, o)
+        return PolicyCollection(obs_out, acts, rew, flags[:rows], ret, o)
 
     def lookahead_policy(self, policy, fanout, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, keep_mean=False,
                          return_rewards=False, return_best=False, return_actions=False, return_end=False):

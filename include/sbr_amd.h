@@ -463,6 +463,27 @@ int64_t sbr_policy_param_count(int32_t n_hidden, int32_t width);
 int sbr_rollout_policy(sbr_env* env, int32_t n_steps, int32_t hold, const sbr_policy* policy, float* obs, double* returns,
                        float* actions_out, double* rewards_out, void* stream);
 
+/* sbr_rollout_policy as a COLLECTOR: the same launch, which also reports, for every decision, the observation it was taken on
+ * and whether its transition is terminal - the (obs_d, action_d, reward_d, ended_d) a gradient-based learner needs.
+ * Every argument shared with sbr_rollout_policy follows that contract word for word and yields THE SAME BITS: the handle's
+ * plant and every controller row, obs on exit, returns, actions_out and rewards_out - for populations, noise and any hold;
+ * done envs skip their calls, the terminal phases run once for the done call, SBR_C_PLAN reads 0 afterwards, nothing is
+ * allocated (graph-capturable).  With rows = ceil(n_steps / hold), decision d taken on call s = d*hold of the launch:
+ *   obs_out     [rows][N][SBR_NOBS] float32 or NULL: the 18 values the net was applied to at decision d, exactly the float32
+ *               values the net's first layer reads.  Row 0 is the env's row of obs on entry.  For an env whose episode had ended
+ *               before the decision: SBR_NOBS zeros (actions_out holds 0 there)
+ *   flags_out   [rows][N] uint8 or NULL: SBR_DF_TAKEN - the decision was taken; SBR_DF_ENDED - the env's episode ended during
+ *               one of this decision's calls (the transition is terminal).  So 0 (skipped), 1 or 3.  A short last decision
+ *               (n_steps not a multiple of hold) is reported like any other
+ * The action MEAN of a decision is a pure function of its obs_out row under the arithmetic fixed at sbr_policy, and is not
+ * reported.  n_steps = 0 touches nothing, writes returns = 0 and leaves obs_out and flags_out unwritten.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): every refusal of sbr_rollout_policy;
+ * obs_out and flags_out both NULL (call sbr_rollout_policy). */
+#define SBR_DF_TAKEN 1
+#define SBR_DF_ENDED 2
+int sbr_collect_policy(sbr_env* env, int32_t n_steps, int32_t hold, const sbr_policy* policy, float* obs, double* returns,
+                       float* actions_out, double* rewards_out, float* obs_out, uint8_t* flags_out, void* stream);
+
 /* CLOSED-LOOP lookahead: `fanout` rollouts of the caller's policy per env, each from the env's CURRENT state and observation, the
  * handle left bit for bit as it was (Monte-Carlo value and advantage estimates at the states the learner visits, policy-guided
  * MPC, n-step returns plus a critic on obs_end).  sbr_rollout_policy in the read-only, K-branches-per-env form of

@@ -5,8 +5,10 @@ refactor of the device code has to show.  usage: python scripts/isa_compare.py b
     spills, scratch and LDS from the code object's metadata, the float64 mix of the Butcher-5 and RK4 step loops as tests/isa.py
     picks them, the vector stores and the instruction count - one row per build, before -> after where they differ;
   * every OTHER kernel: the instruction text (instructions and local labels, the function number taken out of the labels) must
-    be identical.
-Exit status 1 if an unnamed kernel moved, or if a named build grew in any figure but the instruction count's decrease."""
+    be identical;
+  * the kernels named by --added (none by default) are expected in `after` only and are listed with the same figures.
+Exit status 1 if an unnamed kernel moved, if a named build grew in any figure but the instruction count's decrease, or if the
+two kernel lists differ by anything but the added kernels."""
 import argparse
 import os
 import re
@@ -58,6 +60,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("before"); ap.add_argument("after")
     ap.add_argument("--changed", nargs="*", default=list(FUSED))
+    ap.add_argument("--added", nargs="*", default=[], help="kernels expected in `after` only: listed with their figures")
     ap.add_argument("-o", "--out")
     a = ap.parse_args()
     with open(a.before) as f:
@@ -66,9 +69,10 @@ def main():
         after = f.read()
     kb, ka = kernels(before), kernels(after)
     lines, bad = [], 0
-    if sorted(kb) != sorted(ka):
+    added = sorted(s for s in set(ka) - set(kb) if base_name(s) in a.added)
+    if sorted(kb) != sorted(set(ka) - set(added)):
         bad += 1
-        lines.append("kernel lists differ: only before %s, only after %s" % (sorted(set(kb) - set(ka)), sorted(set(ka) - set(kb))))
+        lines.append("kernel lists differ: only before %s, only after %s" % (sorted(set(kb) - set(ka)), sorted(set(ka) - set(kb) - set(added))))
     named = [s for s in kb if base_name(s) in a.changed and s in ka]
     others = [s for s in kb if base_name(s) not in a.changed and s in ka]
     moved = [s for s in others if text_key(isa.kernel_text(before, s)) != text_key(isa.kernel_text(after, s))]
@@ -94,6 +98,17 @@ def main():
     width = [max(len(r[i]) for r in rows) for i in range(len(head))]
     lines += ["  ".join(c.ljust(w) for c, w in zip(r, width)).rstrip() for r in rows]
     lines.append("")
+    if added:
+        lines.append("%d builds of the added kernels (%s), in `after` only" % (len(added), ", ".join(a.added)))
+        rows = [head]
+        for s in added:
+            f = figures(after, s)
+            mixes = sorted(set(f["b5_mix"] + f["rk4_mix"]))
+            rows.append((s,) + tuple(str(f[k]) for k in META) + (str(len(f["b5_mix"])), str(len(f["rk4_mix"])),
+                                                                 "%d distinct" % len(mixes), str(f["stores"]), str(f["instructions"])))
+        width = [max(len(r[i]) for r in rows) for i in range(len(head))]
+        lines += ["  ".join(c.ljust(w) for c, w in zip(r, width)).rstrip() for r in rows]
+        lines.append("")
     lines.append("%d failures" % bad)
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
