@@ -33,29 +33,26 @@ class SbrEnv2Vec(SbrOSVec):
                                             _ptr(self.diag) if want_diag else None, self._stream()), self._h)
         return self.cobs, self.reward, self.all_done
 
-    def rollout(self, *a, **k):
-        raise NotImplementedError("the fused random-policy rollout belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 
-    def lookahead(self, *a, **k):
-        raise NotImplementedError("the read-only lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+# The fused entry points of SbrOSVec that SBR-v2 refuses, and what each is called in the refusal.
+_REFUSED = {
+    "rollout": "the fused random-policy rollout",
+    "lookahead": "the read-only lookahead",
+    "lookahead_sampled": "the sampled lookahead",
+    "lookahead_end": "the read-only lookahead",
+    "lookahead_sampled_end": "the sampled lookahead",
+    "lookahead_policy": "the closed-loop lookahead",
+    "collect_policy": "the fused policy collector",
+    "branch_best": "the winner of a lookahead's branches",
+    "mppi_update": "the MPPI tape update",
+}
 
-    def lookahead_sampled(self, *a, **k):
-        raise NotImplementedError("the sampled lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 
-    def lookahead_end(self, *a, **k):
-        raise NotImplementedError("the read-only lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+def _refusal(phrase):
+    def refuse(self, *a, **k):            # before it looks at an argument
+        raise NotImplementedError(phrase + " belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+    return refuse
 
-    def lookahead_sampled_end(self, *a, **k):
-        raise NotImplementedError("the sampled lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
 
-    def lookahead_policy(self, *a, **k):
-        raise NotImplementedError("the closed-loop lookahead belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
-
-    def collect_policy(self, *a, **k):
-        raise NotImplementedError("the fused policy collector belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
-
-    def branch_best(self, *a, **k):
-        raise NotImplementedError("the winner of a lookahead's branches belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
-
-    def mppi_update(self, *a, **k):
-        raise NotImplementedError("the MPPI tape update belongs to SBROS-v1; SBR-v2 already runs a whole cycle per launch")
+for _name, _phrase in _REFUSED.items():
+    setattr(SbrEnv2Vec, _name, _refusal(_phrase))

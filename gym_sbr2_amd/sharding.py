@@ -7,8 +7,12 @@ all-gather of the per-env episode returns per episode (RCCL over xGMI on the GPU
 The reference has nothing distributed; this is the MI355X-side design for
 BASELINE.json configs[3].
 """
+import functools
+
 import torch
 import torch.distributed as dist
+
+from . import vec_env
 
 
 def shard_range(n_global, rank, world):
@@ -102,67 +106,6 @@ class ShardedSbrOS:
     def step(self, action):
         return self.env.step(action)
 
-    def rollout(self, n_steps, policy_seed=0):
-        return self.env.rollout(n_steps, policy_seed)
-
-    def rollout_actions(self, actions, n_steps=None, hold=1, return_rewards=False):
-        """SbrOSVec.rollout_actions for this rank's block: `actions` [R, n_local, 2] is the rank's own slice of the tape
-        (columns start .. stop - 1 of the global one)."""
-        return self.env.rollout_actions(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards)
-
-    def lookahead(self, actions, n_steps=None, hold=1, return_rewards=False, return_best=False):
-        """SbrOSVec.lookahead for this rank's block: `actions` [R, n_local, K, 2] is the rank's own slice of the candidates
-        (columns start .. stop - 1 of the global ones)."""
-        return self.env.lookahead(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards, return_best=return_best)
-
-    def lookahead_sampled(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
-                          return_actions=False):
-        """SbrOSVec.lookahead_sampled for this rank's block: `nominal` [R, n_local, 2] is the rank's own slice of the nominal
-        tape.  The candidates are keyed by the global env id, so the results do not depend on the world size."""
-        return self.env.lookahead_sampled(nominal, fanout, sampler, n_steps=n_steps, hold=hold, return_rewards=return_rewards,
-                                          return_best=return_best, return_actions=return_actions)
-
-    def lookahead_end(self, actions, n_steps=None, hold=1, return_rewards=False, return_best=False):
-        """SbrOSVec.lookahead_end for this rank's block (`actions` and every result are the rank's own slices)."""
-        return self.env.lookahead_end(actions, n_steps=n_steps, hold=hold, return_rewards=return_rewards, return_best=return_best)
-
-    def lookahead_sampled_end(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
-                              return_actions=False):
-        """SbrOSVec.lookahead_sampled_end for this rank's block (`nominal` and every result are the rank's own slices)."""
-        return self.env.lookahead_sampled_end(nominal, fanout, sampler, n_steps=n_steps, hold=hold, return_rewards=return_rewards,
-                                              return_best=return_best, return_actions=return_actions)
-
-    def branch_best(self, values):
-        """SbrOSVec.branch_best for this rank's block: `values` [n_local, K] is the rank's own slice."""
-        return self.env.branch_best(values)
-
-    def mppi_update(self, nominal, returns, sampler, temperature, shift=0, out=None, return_weights=False):
-        """SbrOSVec.mppi_update for this rank's block (`nominal`, `returns` and `out` are the rank's own slices)."""
-        return self.env.mppi_update(nominal, returns, sampler, temperature, shift=shift, out=out, return_weights=return_weights)
-
-    def rollout_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, return_actions=False,
-                       return_rewards=False):
-        """SbrOSVec.rollout_policy for this rank's block.  `policy` is the WHOLE population on every rank: an env picks its
-        member by its global id, so the result does not depend on the world size (with more than one member the rank's first
-        global id must be a multiple of 256).  `obs` [n_local, 18] is the rank's own slice."""
-        return self.env.rollout_policy(policy, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed,
-                                       return_actions=return_actions, return_rewards=return_rewards)
-
-    def collect_policy(self, policy, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0):
-        """SbrOSVec.collect_policy for this rank's block (`obs` [n_local, 18] and every field of the result are the rank's own
-        slices).  `policy` is the WHOLE population on every rank, as in rollout_policy, and the noise is keyed by the global env
-        id, so the result does not depend on the world size."""
-        return self.env.collect_policy(policy, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed)
-
-    def lookahead_policy(self, policy, fanout, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, keep_mean=False,
-                         return_rewards=False, return_best=False, return_actions=False, return_end=False):
-        """SbrOSVec.lookahead_policy for this rank's block (`obs` [n_local, 18] and every result are the rank's own slices).
-        `policy` is the WHOLE population on every rank, as in rollout_policy; the noise of a branch is keyed by its env's global
-        id and its index among the env's branches, so the results do not depend on the world size."""
-        return self.env.lookahead_policy(policy, fanout, n_steps, hold=hold, obs=obs, noise_std=noise_std, noise_seed=noise_seed,
-                                         keep_mean=keep_mean, return_rewards=return_rewards, return_best=return_best,
-                                         return_actions=return_actions, return_end=return_end)
-
     def gather_buffers(self, dtype=torch.float32):
         """Caller-owned buffers for gather_episode_returns_into(): (float64 row [n_local], send [n_local] dtype, recv [n_global]
         dtype) on this rank's device.  Only equal shards can be gathered without staging (all_gather_into_tensor)."""
@@ -186,3 +129,39 @@ class ShardedSbrOS:
 
     def close(self):
         self.env.close()
+
+
+# What a shard passes through to its SbrOSVec unchanged - arguments and results are the rank's own block - and the one sentence
+# each adds to the original's docstring.  Built at import: a name SbrOSVec does not have fails here.
+_WHOLE_POPULATION = ("`policy` is the WHOLE population on every rank: an env picks its member by its global id, so the result does "
+                     "not depend on the world size (with more than one member the rank's first global id must be a multiple of 256)")
+_FORWARDED = {
+    "rollout": "The random policy is keyed by the global env id, so the returns do not depend on the world size.",
+    "rollout_actions": "`actions` [R, n_local, 2] is the rank's own slice of the tape (columns start .. stop - 1 of the global one).",
+    "lookahead": "`actions` [R, n_local, K, 2] is the rank's own slice of the candidates (columns start .. stop - 1 of the global ones).",
+    "lookahead_end": "`actions` and every result are the rank's own slices.",
+    "lookahead_sampled": "`nominal` [R, n_local, 2] is the rank's own slice of the nominal tape; the candidates are keyed by the global "
+                         "env id, so the results do not depend on the world size.",
+    "lookahead_sampled_end": "`nominal` and every result are the rank's own slices.",
+    "branch_best": "`values` [n_local, K] is the rank's own slice.",
+    "mppi_update": "`nominal`, `returns` and `out` are the rank's own slices.",
+    "rollout_policy": _WHOLE_POPULATION + "; `obs` [n_local, 18] is the rank's own slice.",
+    "collect_policy": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every field of the result are the rank's own slices, and the "
+                      "noise is keyed by the global env id.",
+    "lookahead_policy": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every result are the rank's own slices, and the noise of a "
+                        "branch is keyed by its env's global id and its index among the env's branches.",
+}
+
+
+def _forwarder(name, sentence):
+    original = getattr(vec_env.SbrOSVec, name)
+
+    @functools.wraps(original)            # the original's signature, for inspect.signature and help()
+    def method(self, *args, **kwargs):
+        return getattr(self.env, name)(*args, **kwargs)
+    method.__doc__ = "%s ...\n\nSbrOSVec.%s for this rank's block.  %s" % (original.__doc__.splitlines()[0], name, sentence)
+    return method
+
+
+for _name, _sentence in _FORWARDED.items():
+    setattr(ShardedSbrOS, _name, _forwarder(_name, _sentence))

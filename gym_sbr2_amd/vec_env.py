@@ -295,30 +295,35 @@ class SbrOSVec:
         At least one call: n_steps = 0 is refused."""
         return self._lookahead(actions, n_steps, hold, return_rewards, return_best, True)
 
-    def _end_outputs(self, fanout):
-        n, dev = self.num_envs, self.device
-        return (torch.empty((n, fanout, _capi.NOBS), dtype=torch.float32, device=dev),
-                torch.empty((n, fanout, _capi.NSTATE), dtype=torch.float32, device=dev),
-                torch.empty((n, fanout), dtype=torch.bool, device=dev))        # one byte per branch, written as 0 / 1
-
-    def _lookahead(self, actions, n_steps, hold, return_rewards, return_best, end):
-        hold = int(hold)
-        a, rows, n_steps = self._tape(actions, (self.num_envs, None, 2), n_steps, hold)
-        fanout = int(a.shape[2])
+    def _fanout_outputs(self, fanout, n_steps, hold, return_rewards, return_best, return_end, return_actions=False,
+                        actions_dtype=None):
+        """What a fan-out launch writes, sized once for lookahead, lookahead_sampled and lookahead_policy (and their _end forms).
+        Returns (ptrs, end_ptrs, results).  `ptrs` is in the ABI's order: returns, rewards, best_index, best_return and - only
+        for a call that has the output at all, actions_dtype not None - actions; `end_ptrs` is obs_end, state_end, done_end.  An
+        output that was not asked for is a None pointer.  `results` is what the method returns, in the one public order:
+        returns, rewards, best_index, best_return, actions, obs_end, state_end, done_end - those asked for."""
         n, dev = self.num_envs, self.device
         ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
         rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
         bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
         br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
-        ends = self._end_outputs(fanout) if end else ()
-        if end:
-            _capi.check(self.lib.sbr_lookahead_actions_end(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, _ptr(ret),
-                                                           _ptr(rew), _ptr(bi), _ptr(br), *[_ptr(t) for t in ends], self._stream()),
-                        self._h)
-        else:
-            _capi.check(self.lib.sbr_lookahead_actions(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, _ptr(ret), _ptr(rew),
-                                                       _ptr(bi), _ptr(br), self._stream()), self._h)
-        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ()) + ends)
+        acts = torch.empty((-(-n_steps // hold), n, fanout, 2), dtype=actions_dtype, device=dev) if return_actions else None
+        ends = (torch.empty((n, fanout, _capi.NOBS), dtype=torch.float32, device=dev),
+                torch.empty((n, fanout, _capi.NSTATE), dtype=torch.float32, device=dev),
+                torch.empty((n, fanout), dtype=torch.bool, device=dev)) if return_end else (None,) * 3   # bool: one byte, 0 / 1
+        outs = (ret, rew, bi, br) + ((acts,) if actions_dtype is not None else ())
+        return ([_ptr(t) for t in outs], [_ptr(t) for t in ends],
+                _one_or_all(tuple(t for t in (ret, rew, bi, br, acts) + ends if t is not None)))
+
+    def _lookahead(self, actions, n_steps, hold, return_rewards, return_best, end):
+        hold = int(hold)
+        a, rows, n_steps = self._tape(actions, (self.num_envs, None, 2), n_steps, hold)
+        fanout = int(a.shape[2])
+        ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_steps, hold, return_rewards, return_best, end)
+        fn = self.lib.sbr_lookahead_actions_end if end else self.lib.sbr_lookahead_actions
+        _capi.check(fn(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, *ptrs, *(end_ptrs if end else ()),
+                       self._stream()), self._h)
+        return results
 
     def lookahead_sampled(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_best=False,
                           return_actions=False):
@@ -340,22 +345,12 @@ class SbrOSVec:
         hold, fanout = int(hold), int(fanout)
         a, rows, n_steps = self._tape(nominal, self._ashape, n_steps, hold)
         sm = sampler.c_struct(self.cfg)
-        n, dev = self.num_envs, self.device
-        ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
-        rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
-        bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
-        br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
-        acts = torch.empty((-(-n_steps // hold), n, fanout, 2), dtype=self.action_dtype, device=dev) if return_actions else None
-        ends = self._end_outputs(fanout) if end else ()
-        if end:
-            _capi.check(self.lib.sbr_lookahead_sampled_end(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm),
-                                                           _ptr(ret), _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts),
-                                                           *[_ptr(t) for t in ends], self._stream()), self._h)
-        else:
-            _capi.check(self.lib.sbr_lookahead_sampled(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm), _ptr(ret),
-                                                       _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts), self._stream()), self._h)
-        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ())
-                           + ((acts,) if return_actions else ()) + ends)
+        ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_steps, hold, return_rewards, return_best, end, return_actions,
+                                                       self.action_dtype)
+        fn = self.lib.sbr_lookahead_sampled_end if end else self.lib.sbr_lookahead_sampled
+        _capi.check(fn(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm), *ptrs, *(end_ptrs if end else ()),
+                       self._stream()), self._h)
+        return results
 
     def branch_best(self, values):
         """The winner among each env's K values (sbr_branch_best), under the rule of lookahead's best_*: the largest value wins,
@@ -419,9 +414,9 @@ class SbrOSVec:
         self._policy_obs_back(obs, o)
         return _one_or_all((ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ()))
 
-    def _policy_inputs(self, policy, n_steps, hold, obs, noise_std, noise_seed):
-        """What rollout_policy and collect_policy hand the library: the in/out observation (obs=None: self.obs, as float32) and
-        the sbr_policy struct."""
+    def _policy_inputs(self, policy, n_steps, hold, obs, noise_std, noise_seed, in_place=True):
+        """What rollout_policy, collect_policy and lookahead_policy hand the library: the observation (obs=None: self.obs, as
+        float32) and the sbr_policy struct.  in_place: the launch writes the observation (lookahead_policy only reads it)."""
         if hold < 1:
             raise ValueError("hold must be >= 1")
         if n_steps < 0:
@@ -432,8 +427,8 @@ class SbrOSVec:
             o = o.to(torch.float32)
         if not (isinstance(o, torch.Tensor) and o.dtype == torch.float32 and o.device == self.device and o.is_contiguous()
                 and tuple(o.shape) == (self.num_envs, _capi.NOBS)):
-            raise ValueError("obs must be a contiguous float32 tensor of shape [N,%d] on %s (it is updated in place)"
-                             % (_capi.NOBS, self.device))
+            raise ValueError("obs must be a contiguous float32 tensor of shape [N,%d] on %s%s"
+                             % (_capi.NOBS, self.device, " (it is updated in place)" if in_place else ""))
         pol = policy.c_struct(self.device, noise_std=noise_std, noise_seed=noise_seed)
         self._keep_p = (policy, pol, o)
         return o, pol
@@ -484,32 +479,14 @@ class SbrOSVec:
         they were integrated (fed to lookahead they give the same bits); obs_end [N, K, 18], state_end [N, K, 15] and done_end
         [N, K] as lookahead_end gives them (n_steps = 0 is then refused)."""
         n_steps, hold, fanout = int(n_steps), int(hold), int(fanout)
-        if hold < 1:
-            raise ValueError("hold must be >= 1")
-        if n_steps < 0:
-            raise ValueError("n_steps must be >= 0")
-        n, dev = self.num_envs, self.device
-        if fanout < 1 or fanout > 2 ** 24 or n * fanout >= 2 ** 31:      # before the outputs are sized by it
+        if fanout < 1 or fanout > 2 ** 24 or self.num_envs * fanout >= 2 ** 31:      # before the outputs are sized by it
             raise ValueError("fanout must be in 1 .. 2^24 with num_envs * fanout below 2^31")
-        o = self.obs if obs is None else obs
-        if obs is None and o.dtype != torch.float32:
-            o = o.to(torch.float32)
-        if not (isinstance(o, torch.Tensor) and o.dtype == torch.float32 and o.device == dev and o.is_contiguous()
-                and tuple(o.shape) == (n, _capi.NOBS)):
-            raise ValueError("obs must be a contiguous float32 tensor of shape [N,%d] on %s" % (_capi.NOBS, dev))
-        pol = policy.c_struct(dev, noise_std=noise_std, noise_seed=noise_seed)
-        self._keep_p = (policy, pol, o)
-        ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
-        rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
-        bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
-        br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
-        acts = torch.empty((-(-n_steps // hold), n, fanout, 2), dtype=torch.float32, device=dev) if return_actions else None
-        ends = self._end_outputs(fanout) if return_end else (None, None, None)
+        o, pol = self._policy_inputs(policy, n_steps, hold, obs, noise_std, noise_seed, in_place=False)
+        ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_steps, hold, return_rewards, return_best, return_end,
+                                                       return_actions, torch.float32)
         _capi.check(self.lib.sbr_lookahead_policy(self._h, n_steps, hold, fanout, C.byref(pol), 1 if keep_mean else 0, _ptr(o),
-                                                  _ptr(ret), _ptr(rew), _ptr(bi), _ptr(br), _ptr(acts), *[_ptr(t) for t in ends],
-                                                  self._stream()), self._h)
-        return _one_or_all((ret,) + ((rew,) if return_rewards else ()) + ((bi, br) if return_best else ())
-                           + ((acts,) if return_actions else ()) + (ends if return_end else ()))
+                                                  *ptrs, *end_ptrs, self._stream()), self._h)
+        return results
 
     def enable_trace(self, n_envs=1, capacity=463):
         """Trajectory export: every step() appends one record (_capi.TR_*: t, x(14), Kla, EC, reward, done, the set-points in

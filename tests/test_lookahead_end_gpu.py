@@ -22,7 +22,8 @@ The other seven builds of each differ from these in template arguments the kerne
 (tests/test_tape_rollout_gpu.py runs those under every argument) and are not run here."""
 import numpy as np
 import pytest
-from gpu_common import STEPS, package
+from gpu_common import (STEPS, host_best as _host_best, live as _live, nominal as _nominal, package, same as _same,
+                        tape as _tape)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -31,29 +32,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def G():
     return package()
-
-
-def _live(G, n, calls, seed, **kw):
-    """A handle of n envs (scenario = id % 8), advanced `calls` calls through step() under varied actions: its controller
-    record is then in the form k_step leaves."""
-    rs = np.random.RandomState(seed)
-    env = G.SbrOSVec(n, **kw)
-    env.reset(scenario=(np.arange(n) % 8).astype(np.int32), rnd=rs.randn(n, 48))
-    acts = np.stack([rs.uniform(0, 2.5, (calls, n)), rs.uniform(0, 15, (calls, n))], axis=-1)
-    acts = torch.from_numpy(acts).to(env.action_dtype).cuda()
-    for c in range(calls):
-        env.step(acts[c])
-    return env
-
-
-def _tape(rows, n, k, seed, dtype=torch.float32):
-    rs = np.random.RandomState(seed)
-    t = np.stack([rs.uniform(0, 2.5, (rows, n, k)), rs.uniform(0, 15, (rows, n, k))], axis=-1)
-    return torch.from_numpy(t).to(dtype).cuda()
-
-
-def _nominal(rows, n, seed, dtype=torch.float32):
-    return _tape(rows, n, 1, seed, dtype)[:, :, 0].contiguous()
 
 
 def _sampler(seed=5):
@@ -80,12 +58,6 @@ def _end_checker(G, a_env, tape, n_steps, hold, **kw):
     torch.cuda.synchronize()
     b_env.close()
     return obs, state, done.reshape(n, k)
-
-
-def _same(a, b):
-    """torch.equal with NaN equal to NaN (a NaN plant gives NaN rows on both sides)."""
-    return a.shape == b.shape and a.dtype == b.dtype and bool((torch.isnan(a) == torch.isnan(b)).all()) and torch.equal(
-        torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0))
 
 
 def _ends_are(got, want, same=torch.equal):
@@ -305,13 +277,6 @@ def test_optional_outputs_and_refusals_on_a_live_handle(G):
     assert torch.equal(x0, x1) and torch.equal(c0, c1)
     assert bool((ret == 7.0).all()) and bool((o == 7.0).all()) and bool((s == 7.0).all()) and bool((d == 7).all()) and bool((bi == 7).all())
     a_env.close()
-
-
-def _host_best(v):
-    """The header's rule on the host: NaN -> -inf, first maximum; the value is the winner's entry as it stands."""
-    r = v.cpu().numpy()
-    idx = np.argmax(np.where(np.isnan(r), -np.inf, r), axis=1).astype(np.int32)
-    return idx, r[np.arange(r.shape[0]), idx]
 
 
 def test_branch_best(G):

@@ -17,7 +17,7 @@ The other seven builds differ from these in template arguments the kernel only p
 (tests/test_tape_rollout_gpu.py runs those under every argument) and are not run here."""
 import numpy as np
 import pytest
-from gpu_common import STEPS, package
+from gpu_common import STEPS, host_best as _host_best, live as _live, package, tape as _tape
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -26,25 +26,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def G():
     return package()
-
-
-def _live(G, n, calls, seed, **kw):
-    """A handle of n envs (scenario = id % 8), advanced `calls` calls through step() under varied actions: its controller
-    record is then in the form k_step leaves (implicit So[-1] / Sno[-1], the Kla ring rotated, a non-zero plan row)."""
-    rs = np.random.RandomState(seed)
-    env = G.SbrOSVec(n, **kw)
-    env.reset(scenario=(np.arange(n) % 8).astype(np.int32), rnd=rs.randn(n, 48))
-    acts = np.stack([rs.uniform(0, 2.5, (calls, n)), rs.uniform(0, 15, (calls, n))], axis=-1)
-    acts = torch.from_numpy(acts).to(env.action_dtype).cuda()
-    for c in range(calls):
-        env.step(acts[c])
-    return env
-
-
-def _tape(rows, n, k, seed, dtype=torch.float32):
-    rs = np.random.RandomState(seed)
-    t = np.stack([rs.uniform(0, 2.5, (rows, n, k)), rs.uniform(0, 15, (rows, n, k))], axis=-1)
-    return torch.from_numpy(t).to(dtype).cuda()
 
 
 def _checker(G, a_env, tape, n_steps, hold, **kw):
@@ -63,13 +44,6 @@ def _checker(G, a_env, tape, n_steps, hold, **kw):
 def _same(a, b):
     """torch.equal with NaN equal to NaN (a NaN plant gives NaN rewards on both sides)."""
     return a.shape == b.shape and bool((torch.isnan(a) == torch.isnan(b)).all()) and torch.equal(torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0))
-
-
-def _host_best(ret):
-    """The header's rule on the host: NaN -> -inf, first maximum; best_return is the winner's entry as it stands."""
-    r = ret.cpu().numpy()
-    idx = np.argmax(np.where(np.isnan(r), -np.inf, r), axis=1).astype(np.int32)
-    return idx, r[np.arange(r.shape[0]), idx]
 
 
 def _check_best(ret, bi, br):

@@ -6,8 +6,8 @@ Three checkers, all existing entry points that earlier test files pin:
     observation: without noise every branch, and under noise branch 0, is that rollout bit for bit (same inlined device
     functions, -ffp-contract=off);
   * `lookahead` / `lookahead_end` fed this call's own actions_out: returns, rewards, winners and end rows bit for bit;
-  * a numpy Philox4x32-10 + Box-Muller written here (restated from tests/test_mppi_gpu.py, and anchored to the device's
-    sbr_draw_normals in the same way) for the noise word.
+  * the numpy Philox4x32-10 + Box-Muller of tests/gpu_common.py (anchored here to the device's sbr_draw_normals, as in
+    tests/test_mppi_gpu.py) for the noise word.
 Comparisons are torch.equal with NaN equal to NaN (`_same`).
 
 Which test runs which build of k_lookahead_policy<H, OCI, SCH, WAVES> ((SCH, WAVES) = (1, 1) up to 98 304 BRANCHES, (1, 2) above,
@@ -24,7 +24,8 @@ import ctypes as C
 
 import numpy as np
 import pytest
-from gpu_common import STEPS, package
+from gpu_common import (STEPS, host_best as _host_best, live as _live, net as _net, normal_pair as _normal_pair, package,
+                        same as _same)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -38,19 +39,6 @@ def G():
     return package()
 
 
-def _live(G, n, calls, seed, first=0, **kw):
-    """A handle of n envs with global ids first .. (scenario = id % 8), advanced `calls` calls through step() under varied
-    actions: its controller record is then in the form k_step leaves."""
-    rs = np.random.RandomState(seed)
-    env = G.SbrOSVec(n, first_env_id=first, **kw)
-    env.reset(scenario=((first + np.arange(n)) % 8).astype(np.int32), rnd=rs.randn(n, 48))
-    acts = np.stack([rs.uniform(0, 2.5, (calls, n)), rs.uniform(0, 15, (calls, n))], axis=-1)
-    acts = torch.from_numpy(acts).to(env.action_dtype).cuda()
-    for c in range(calls):
-        env.step(acts[c])
-    return env
-
-
 def _clone(G, env, lo=0, hi=None, **kw):
     """(a second handle holding the envs lo .. hi - 1 of `env` - same global ids, influent and state -, their float32 obs)."""
     hi = env.num_envs if hi is None else hi
@@ -61,21 +49,9 @@ def _clone(G, env, lo=0, hi=None, **kw):
     return b, env.obs[lo:hi].to(torch.float32).clone()
 
 
-def _net(seed, widths):
-    rs = np.random.RandomState(seed)
-    sizes = [18] + list(widths) + [2]
-    return [(rs.randn(o, i) / np.sqrt(i), rs.randn(o) * 0.1) for i, o in zip(sizes[:-1], sizes[1:])]
-
-
 def _policy(seed=13, widths=(32, 32), activation="tanh", squash="tanh"):
     from gym_sbr2_amd import MlpPolicy
     return MlpPolicy(_net(seed, widths), activation=activation, squash=squash, low=LOW, high=HIGH)
-
-
-def _same(a, b):
-    """torch.equal with NaN equal to NaN."""
-    return a.shape == b.shape and a.dtype == b.dtype and bool((torch.isnan(a) == torch.isnan(b)).all()) and torch.equal(
-        torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0))
 
 
 def _state_rows(env):
@@ -128,34 +104,6 @@ def _against_clone(G, env, pol, out, n_steps, hold, branches=None, **kw):
         assert _same(acts[:, :, k], acts_c), k
     clone.close()
     return ret_c, acts_c, rew_c
-
-
-# ------------------------------------------------------------------ Philox4x32-10 + Box-Muller in numpy (include/sbr_amd.h)
-_M32 = np.uint64(0xFFFFFFFF)
-
-
-def _philox(c, key):
-    """c: four uint64 arrays holding 32-bit words; key: the 64-bit seed."""
-    c0, c1, c2, c3 = (np.asarray(v, dtype=np.uint64) & _M32 for v in c)
-    k0, k1 = np.uint64(key & 0xFFFFFFFF), np.uint64((key >> 32) & 0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
-    return c0, c1, c2, c3
-
-
-def _normal_pair(counter, stream, gid, seed):
-    """(z0, z1) of Philox block (counter, stream, gid_lo, gid_hi) under key `seed`; the arguments broadcast."""
-    counter, stream, gid = np.broadcast_arrays(*(np.asarray(v, dtype=np.uint64) for v in (counter, stream, gid)))
-    c = _philox((counter, stream, gid & _M32, gid >> np.uint64(32)), seed)
-
-    def u53(hi, lo):                                   # uniform in (0, 1]
-        return (((hi << np.uint64(32)) | lo) >> np.uint64(11)).astype(np.float64) + 1.0
-
-    u1, u2 = u53(c[0], c[1]) * 2.0 ** -53, u53(c[2], c[3]) * 2.0 ** -53
-    rad, ang = np.sqrt(-2.0 * np.log(u1)), 6.283185307179586476925286766559 * u2
-    return rad * np.cos(ang), rad * np.sin(ang)
 
 
 def _noise_bound_holds(acts, mean, counter, gid, seed):
@@ -247,13 +195,6 @@ def test_branch_0_under_noise_and_keep_mean(G):
 
 
 # ------------------------------------------------------------------ 4
-def _host_best(v):
-    """The header's rule on the host: NaN -> -inf, first maximum; the value is the winner's entry as it stands."""
-    r = v.cpu().numpy()
-    idx = np.argmax(np.where(np.isnan(r), -np.inf, r), axis=1).astype(np.int32)
-    return idx, r[np.arange(r.shape[0]), idx]
-
-
 def test_chain_to_the_tape_kernel_across_wavefronts_and_the_workgroup_boundary(G):
     """N = 4, K = 70: 280 branches - an env's branches straddle wavefronts and the 256-lane workgroup boundary.  Env 3: NaN
     ammonia injected through set_state (NaN observations, actions and returns: index 0, NaN)."""

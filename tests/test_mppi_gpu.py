@@ -3,8 +3,8 @@ of the nominal tape with the candidates drawn again.
 
 The checker of the sampled lookahead is the EXISTING lookahead (`lookahead`, itself pinned bit for bit to the tape kernel by
 tests/test_lookahead_gpu.py) fed the new kernel's own actions_out: same inlined device functions, -ffp-contract=off, so returns,
-per-call rewards and the winner are compared with torch.equal - no tolerance.  The sample itself is checked against a numpy
-Philox4x32-10 + Box-Muller written here and first anchored to the device's sbr_draw_normals; the update against float64 on the
+per-call rewards and the winner are compared with torch.equal - no tolerance.  The sample itself is checked against the numpy
+Philox4x32-10 + Box-Muller of tests/gpu_common.py, first anchored here to the device's sbr_draw_normals; the update against float64 on the
 host, with the bounds derived in the tests' docstrings.
 
 Which test runs which build of k_lookahead_sampled<ActT, OCI, SCH, WAVES> ((SCH, WAVES) = (1, 1) up to 98 304 BRANCHES, (1, 2) above,
@@ -20,7 +20,7 @@ import math
 
 import numpy as np
 import pytest
-from gpu_common import STEPS, package
+from gpu_common import STEPS, live as _live, nominal as _nominal, normal_pair as _normal_pair, package, same as _same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -29,31 +29,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def G():
     return package()
-
-
-def _live(G, n, calls, seed, first=0, **kw):
-    """A handle of n envs with global ids first .. (scenario = id % 8), advanced `calls` calls through step() under varied
-    actions: its controller record is then in the form k_step leaves."""
-    rs = np.random.RandomState(seed)
-    env = G.SbrOSVec(n, first_env_id=first, **kw)
-    env.reset(scenario=((first + np.arange(n)) % 8).astype(np.int32), rnd=rs.randn(n, 48))
-    acts = np.stack([rs.uniform(0, 2.5, (calls, n)), rs.uniform(0, 15, (calls, n))], axis=-1)
-    acts = torch.from_numpy(acts).to(env.action_dtype).cuda()
-    for c in range(calls):
-        env.step(acts[c])
-    return env
-
-
-def _nominal(rows, n, seed, dtype=torch.float32, lo=(0.0, 0.0), hi=(2.5, 15.0)):
-    rs = np.random.RandomState(seed)
-    t = np.stack([rs.uniform(lo[0], hi[0], (rows, n)), rs.uniform(lo[1], hi[1], (rows, n))], axis=-1)
-    return torch.from_numpy(t).to(dtype).cuda()
-
-
-def _same(a, b):
-    """torch.equal with NaN equal to NaN."""
-    return a.shape == b.shape and a.dtype == b.dtype and bool((torch.isnan(a) == torch.isnan(b)).all()) and torch.equal(
-        torch.nan_to_num(a, nan=-7.0), torch.nan_to_num(b, nan=-7.0))
 
 
 def _against_lookahead(env, nominal, fanout, sampler, n_steps, hold):
@@ -67,34 +42,6 @@ def _against_lookahead(env, nominal, fanout, sampler, n_steps, hold):
     ret_l, rew_l, bi_l, br_l = env.lookahead(acts, n_steps=n_steps, hold=hold, return_rewards=True, return_best=True)
     assert _same(ret, ret_l) and _same(rew, rew_l) and torch.equal(bi, bi_l) and _same(br, br_l)
     return ret, rew, bi, br, acts
-
-
-# ------------------------------------------------------------------ Philox4x32-10 + Box-Muller in numpy (include/sbr_amd.h)
-_M32 = np.uint64(0xFFFFFFFF)
-
-
-def _philox(c, key):
-    """c: four uint64 arrays holding 32-bit words; key: the 64-bit seed."""
-    c0, c1, c2, c3 = (np.asarray(v, dtype=np.uint64) & _M32 for v in c)
-    k0, k1 = np.uint64(key & 0xFFFFFFFF), np.uint64((key >> 32) & 0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
-    return c0, c1, c2, c3
-
-
-def _normal_pair(counter, stream, gid, seed):
-    """(z0, z1) of Philox block (counter, stream, gid_lo, gid_hi) under key `seed`; the arguments broadcast."""
-    counter, stream, gid = np.broadcast_arrays(*(np.asarray(v, dtype=np.uint64) for v in (counter, stream, gid)))
-    c = _philox((counter, stream, gid & _M32, gid >> np.uint64(32)), seed)
-
-    def u53(hi, lo):                                   # uniform in (0, 1]
-        return (((hi << np.uint64(32)) | lo) >> np.uint64(11)).astype(np.float64) + 1.0
-
-    u1, u2 = u53(c[0], c[1]) * 2.0 ** -53, u53(c[2], c[3]) * 2.0 ** -53
-    rad, ang = np.sqrt(-2.0 * np.log(u1)), 6.283185307179586476925286766559 * u2
-    return rad * np.cos(ang), rad * np.sin(ang)
 
 
 def test_same_bits_as_lookahead_on_its_own_actions_and_the_handle_is_untouched(G):

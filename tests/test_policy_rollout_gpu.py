@@ -33,7 +33,8 @@ Which test runs which build of k_rollout_policy<H, OCI, SCH, WAVES> (the host pi
 pl.squash == 0: test_squash_none; every other test squashes with tanh."""
 import numpy as np
 import pytest
-from gpu_common import CONFIGS, FLAGS, STEPS, handle as _handle, inputs as _inputs, no_flags, package, to_np as _np
+from gpu_common import (CONFIGS, FLAGS, STEPS, handle as _handle, inputs as _inputs, net as _net, no_flags, package,
+                        to_np as _np)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -45,12 +46,6 @@ U = 2.0 ** -24
 @pytest.fixture(scope="module")
 def G():
     return package()
-
-
-def _net(seed, widths):
-    rs = np.random.RandomState(seed)
-    sizes = [18] + list(widths) + [2]
-    return [(rs.randn(o, i) / np.sqrt(i), rs.randn(o) * 0.1) for i, o in zip(sizes[:-1], sizes[1:])]
 
 
 def _policy(seed, widths, activation="tanh"):
