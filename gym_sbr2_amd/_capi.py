@@ -84,6 +84,7 @@ SYMBOLS = {
     "sbr_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_cycle_reset": (C.c_int, [_VP, _U64, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     "sbr_cycle_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_cycle_lookahead": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_rollout": (C.c_int, [_VP, _I32, _U64, _VP, _VP, _VP]),
     "sbr_rollout_actions": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_actions": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -7,3 +7,4 @@
 #include "sbr_policy.hip"
 #include "sbr_policy_lookahead.hip"
 #include "sbr_policy_collect.hip"
+#include "sbr_cycle_lookahead.hip"

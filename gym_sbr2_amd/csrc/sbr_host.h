@@ -109,6 +109,8 @@ template <typename F> static void dispatch(const sbr_env* e, F&& f) {
 template <int SCH> constexpr int kFusedOneWave = SCH == 1 ? 1 : 2;
 // The launch of a fused kernel over `lanes` lanes: the handle's envs, or the branches of a lookahead - the register budget goes by
 // the lanes of THE launch.  kernel(w) names the build for decltype(w)::value waves per SIMD; e->par and e->buf lead its arguments.
+// That order is relied on: k_cycle_lookahead reads SbrPar a second time at offset 0 of its kernel-argument segment
+// (sbr_cycle_lookahead.hip, which asserts the first parameter of each of its builds).
 template <int SCH, typename Kernel, typename... Args>
 static void launch_fused(const sbr_env* e, int64_t lanes, void* stream, Kernel&& kernel, Args... args) {
     const auto fn = fused_waves_for(e, lanes) == 1 ? kernel(std::integral_constant<int, kFusedOneWave<SCH>>{})

@@ -3,7 +3,8 @@ policy-rollout planner on the closed-loop lookahead.
 
 Plumbing only: the candidates are drawn, scored and averaged inside libsbr_amd.so (sbr_lookahead_sampled, sbr_mppi_update,
 sbr_lookahead_policy); nothing here does arithmetic on a candidate.  The sums formed here add the caller's terminal value to a
-return and average an env's returns."""
+return and average an env's returns.  The exception is CycleSetpointSearch for the per-cycle env SBR-v2: its candidates are
+three numbers per cycle, drawn and refitted in torch, and scored by sbr_cycle_lookahead."""
 import ctypes as C
 
 import numpy as np
@@ -91,6 +92,61 @@ class MppiPlanner:
         self.nominal = buf[1:]
         self.decision += 1
         return (buf[0], ret) if return_returns else buf[0]
+
+
+class CycleSetpointSearch:
+    """Which DO set-points should each plant of `env` (an SbrEnv2Vec) run in the cycle it is about to start?  A cross-entropy
+    search on the per-cycle lookahead: per iteration, `K` tapes of `n_cycles` set-point triples are drawn per env around a
+    per-env mean and std (start: 0.5 and 0.25), clamped to [0, 1] and scored from the env's current state (cycle_lookahead, the
+    handle untouched); mean and std are refitted on the best elite_frac of them.  Candidates whose state came NEAR A POLE or
+    went NON-FINITE (status), or whose return is NaN, are left out of the fit and cannot win.  Candidate 0 is always the best
+    tape so far - the all-0.5 tape to begin with - so while that tape is itself clean the plan never scores worse than it.  An
+    env none of whose candidates may win keeps its mean, its std and its best tape so far: only then - the all-0.5 tape is
+    flagged and nothing clean has been drawn - can the returned tape be a flagged one and its value NaN; `status` [N] uint8 holds
+    the winner's bits after plan(), check it before acting.  Plan d draws under seed + d.  The sampling and the fit are plain
+    torch on the device; every return comes from libsbr_amd.so.
+
+        search = CycleSetpointSearch(env, K=64, n_cycles=3, iters=4, elite_frac=0.25, seed=0)
+        action, value = search.plan(); env.step(action); env.reset(influent=..., carry_over=True)
+    """
+    init_mean, init_std, min_std = 0.5, 0.25, 0.02
+
+    def __init__(self, env, K, n_cycles=1, iters=3, elite_frac=0.25, seed=0):
+        self.env, self.K, self.n_cycles, self.iters = env, int(K), int(n_cycles), int(iters)
+        if self.K < 1 or self.n_cycles < 1 or self.iters < 1:
+            raise ValueError("K, n_cycles and iters must be >= 1")
+        self.n_elite, self.seed, self.decision = max(1, min(self.K, int(round(float(elite_frac) * self.K)))), int(seed), 0
+        self.tape = self.status = None          # after plan(): the winning tape [n_cycles, N, 3] float64 and its status bits [N]
+
+    def plan(self):
+        """One decision: (the first cycle's action [N, 3] in the env's action dtype, the tape's return [N] float64 - exactly what
+        cycle_lookahead returns for `self.tape`)."""
+        import torch
+        env, bad_bits = self.env, _capi.ST_NEAR_POLE | _capi.ST_NONFINITE
+        gen = torch.Generator(device=env.device).manual_seed(self.seed + self.decision)
+        shape = (self.n_cycles, env.num_envs, self.K, 3)
+        mean = torch.full(shape[:2] + (1, 3), self.init_mean, dtype=torch.float64, device=env.device)
+        std, best = torch.full_like(mean, self.init_std), mean.clone()
+        for _ in range(self.iters):
+            cand = (mean + std * torch.randn(shape, generator=gen, dtype=torch.float64, device=env.device)).clamp_(0.0, 1.0)
+            cand[:, :, :1] = best
+            cand = cand.to(env.action_dtype).double()            # the values the kernel integrates
+            ret, status = env.cycle_lookahead(cand, return_status=True)
+            out = ((status & bad_bits) != 0) | ret.isnan()
+            top, idx = ret.masked_fill(out, float("-inf")).topk(self.n_elite, dim=1)
+            ok = top > float("-inf")                             # [N, n_elite]: the elite is a candidate that may win
+            elite = cand.gather(2, idx[None, :, :, None].expand(self.n_cycles, -1, -1, 3))
+            w, some = ok.double()[None, :, :, None], ok[:, 0][None, :, None, None]
+            cnt = w.sum(2, keepdim=True).clamp_(min=1.0)
+            fit = (elite * w).sum(2, keepdim=True) / cnt
+            spread = (((elite - fit) ** 2 * w).sum(2, keepdim=True) / cnt).sqrt_().clamp_(min=self.min_std)
+            mean, std = torch.where(some, fit, mean), torch.where(some, spread, std)     # an env with no such candidate keeps its fit ...
+            win = idx[:, :1].masked_fill(~ok[:, :1], 0)                                   # ... and its best tape so far, candidate 0
+            best = cand.gather(2, win[None, :, :, None].expand(self.n_cycles, -1, -1, 3))
+            value, flags = ret.gather(1, win)[:, 0], status.gather(1, win)[:, 0]
+        self.tape, self.status = best[:, :, 0], flags
+        self.decision += 1
+        return self.tape[0].to(env.action_dtype), value
 
 
 class PolicyRolloutPlanner:

@@ -281,6 +281,35 @@ int sbr_cycle_reset(sbr_env* env, uint64_t seed, const int32_t* scenario, const 
 /* replaces SbrEnv2.step(action): every call is a complete episode (done is always true, :161). */
 int sbr_cycle_step(sbr_env* env, const void* action, void* obs, void* reward, double* diag, void* stream);
 
+/* read-only lookahead over WHOLE CYCLES: `fanout` candidate tapes of n_cycles cycles per env, each played from the env's CURRENT
+ * state and stored influent in one launch, the handle left bit for bit as it was (which three DO set-points should this plant
+ * run in the cycle it is about to start, and what does the choice do to the sludge over the next cycles?).
+ * A BRANCH is j = i*fanout + k: env i, candidate k; there are B = N*fanout < 2^31 of them.
+ *   actions     [n_cycles][B][3] ActT, DEVICE pointer - a [n_cycles][N][fanout][3] array has this layout.  Clipped to [0,1] as in
+ *               sbr_cycle_step.
+ *   returns     [B] float64 or NULL: sum of the branch's rewards, added in cycle order from 0.0
+ *   rewards_out [n_cycles][B] float64 or NULL: the reward of every cycle - the double sbr_cycle_step casts to OutT
+ *   best_index  [N] int32 or NULL, best_return [N] float64 or NULL: the winner among each env's `fanout` returns under the rule
+ *               of sbr_lookahead_actions (the largest wins, NaN compares as -inf, ties go to the lowest k), reduced FROM
+ *               `returns` by a second kernel on the same stream: give returns with them
+ *   obs_end     [B][SBR_NCYC_OBS] float64 or NULL: Qeff, COD_eff, Snh_eff/30 of the branch's LAST cycle - the doubles
+ *               sbr_cycle_step casts to OutT
+ *   diag_end    [B][SBR_NCYC_DIAG] float64 or NULL: the diag row of the branch's last cycle
+ *   status_out  [B] uint8 or NULL: the OR of the SBR_ST_* bits of the branch's state at the start and at the end of every cycle
+ *               of the launch, to mask candidates that left the model's domain
+ * Cycle 0 of a branch is sbr_cycle_step on a copy of env i.  Cycle c > 0 starts from the branch's own state after the aerated
+ * idle of cycle c - 1 under env i's stored influent: what sbr_cycle_reset(carry_over = 1, influent = the env's own) followed
+ * by sbr_cycle_step computes, with the same bits in every output.
+ * NOTHING of the handle is written - not the plant, not a controller row, not the influent - and nothing is allocated
+ * (graph-capturable).  The register budget of the launch goes by B, not by N.
+ * n_cycles = 0 writes returns = 0, best_index = 0 and best_return = 0 and reads nothing.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): NULL env; n_cycles < 0; fanout < 1;
+ * N*fanout >= 2^31; actions NULL with n_cycles > 0; best_index or best_return given while returns is NULL; obs_end, diag_end or
+ * status_out given with n_cycles = 0. */
+int sbr_cycle_lookahead(sbr_env* env, int32_t n_cycles, int32_t fanout, const void* actions,
+                        double* returns, double* rewards_out, int32_t* best_index, double* best_return,
+                        double* obs_end, double* diag_end, uint8_t* status_out, void* stream);
+
 /* fused rollout with an on-device uniform random policy (BASELINE.json configs[4]): n_steps step()
  * calls per env in ONE kernel, plant state held in registers; actions ~ U[0,act_DO_max] x
  * U[0,act_EC_max] from Philox keyed by policy_seed, subsequence = global env id, counter = call index.
