@@ -44,7 +44,7 @@ def __getattr__(name):          # torch is imported only when the env classes ar
     if name == "MlpPolicy":
         from .policy import MlpPolicy
         return MlpPolicy
-    if name in ("TapeSampler", "MppiPlanner", "PolicyRolloutPlanner", "CycleSetpointSearch"):
+    if name in ("TapeSampler", "MppiPlanner", "PolicyRolloutPlanner", "CycleSetpointSearch", "RobustCycleSetpointSearch"):
         from . import planner
         return getattr(planner, name)
     raise AttributeError(name)

@@ -85,6 +85,7 @@ SYMBOLS = {
     "sbr_cycle_reset": (C.c_int, [_VP, _U64, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     "sbr_cycle_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_cycle_lookahead": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_cycle_lookahead_scenarios": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_rollout": (C.c_int, [_VP, _I32, _U64, _VP, _VP, _VP]),
     "sbr_rollout_actions": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_actions": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
@@ -108,6 +109,7 @@ SYMBOLS = {
     "sbr_eval_substeps": (C.c_int, [_VP, _I32, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_draw_normals": (C.c_int, [_VP, _U64, _VP, _VP]),
     "sbr_draw_scenarios": (C.c_int, [_VP, _U64, _VP, _VP]),
+    "sbr_draw_influent": (C.c_int, [_VP, _U64, _I32, _I32, _I32, _VP, _VP, _VP]),
     "sbr_synchronize": (C.c_int, [_VP, _VP]),
     "sbr_timer_start": (C.c_int, [_VP, _VP]),
     "sbr_timer_stop": (C.c_int, [_VP, _VP, C.POINTER(C.c_float)]),

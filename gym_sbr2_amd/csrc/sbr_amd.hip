@@ -8,3 +8,4 @@
 #include "sbr_policy_lookahead.hip"
 #include "sbr_policy_collect.hip"
 #include "sbr_cycle_lookahead.hip"
+#include "sbr_cycle_scenarios.hip"

@@ -8,11 +8,12 @@
 //   k_cycle_reset   the reset of the per-cycle env SBR-v2 (its step, k_cycle, is a fused kernel: sbr_rollout.hip)
 //   k_export, k_import, k_m1_explicit   public <-> internal controller layout; implicit So[-1] / Sno[-1] made explicit
 //   k_stats    wavefront (DPP) reductions of a per-env vector -> {sum,min,max,count}
+//   k_draw_influent   influent futures without a reset: the reset's mix per (env, draw) into a caller's buffer (sbr_draw_influent)
 //   k_rhs, k_substeps, k_normals, k_scenarios, k_fill   known-answer helpers for the parity tests, the scenario draw, handle init
 // What bounds them and how the arithmetic is organised for it: sbr_device.h (sbr_rates, sbr_rk4), DESIGN.md sections 3 and 5.
 // k_step is here and not in a unit of its own because its register allocation, and k_substeps', comes out differently when the
 // two are compiled apart (same instructions, other registers; profiles/r15_units_isa.txt): the layout follows the machine code.
-// Entry points: create / destroy / config / query, tables, the resets, trace, step, state get / set, influent, stats, the
+// Entry points: create / destroy / config / query, tables, the resets, trace, step, state get / set, influent and its futures, stats, the
 // known-answer helpers, synchronize and the timers.  The calling thread's error text (sbr_last_error(NULL)) lives here.
 #include "sbr_host.h"
 
@@ -81,9 +82,9 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_import(SbrPar p, SbrBuf b, const 
 }
 
 // scenario of cfg.random_scenario = 1: uniform over the 8 scenarios (np.random.choice(8, 1), gym_SBR_env4.py:107), Philox
-// stream 2 keyed by the seed of this reset, subsequence = global env id
-SBR_DEV int sbr_scenario_draw(uint64_t seed, uint64_t gid) {
-    uint32_t c[4] = {0u, 2u, (uint32_t)gid, (uint32_t)(gid >> 32)};
+// stream 2 keyed by the seed of this reset, subsequence = global env id; draw d of sbr_draw_influent: stream word 2 + 256 * d
+SBR_DEV int sbr_scenario_draw(uint64_t seed, uint64_t gid, uint32_t stream = 2u) {
+    uint32_t c[4] = {0u, stream, (uint32_t)gid, (uint32_t)(gid >> 32)};
     sbr_philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     return (int)(c[0] & (SBR_NSCEN - 1));
 }
@@ -97,8 +98,10 @@ SBR_DEV void stage_tables(double* lds, const double* __restrict__ tables) {
 
 // influent_mixed for one lane (buffer_tank3.py:68-107): series = mean + std*rnd with ONE rnd vector shared by all series,
 // flow-weighted means, sums accumulated in sample order like python's sum().  ld[1..13]; ld[0] is set by the caller.
+// `stream`: the stream word of the device's own normals (sbr_normal_pair; the resets draw under 0).
 SBR_DEV void influent_lane(const double* lds, bool need_tables, int s, const double* __restrict__ rnd,
-                           const double* __restrict__ influent, uint64_t seed, uint64_t gid, int64_t i, double (&ld)[SBR_NX]) {
+                           const double* __restrict__ influent, uint64_t seed, uint64_t gid, int64_t i, double (&ld)[SBR_NX],
+                           uint32_t stream = 0u) {
     if (need_tables) {
         s = s < 0 ? 0 : (s >= SBR_NSCEN ? SBR_NSCEN - 1 : s);        // never index LDS out of range
         const double* mu = lds + s * SBR_TSTRIDE;
@@ -109,7 +112,7 @@ SBR_DEV void influent_lane(const double* lds, bool need_tables, int s, const dou
         for (int kk = 0; kk < SBR_NSAMP; kk += 2) {
             double z[2];
             if (rnd) { z[0] = rnd[i * SBR_NSAMP + kk]; z[1] = rnd[i * SBR_NSAMP + kk + 1]; }
-            else sbr_normal_pair(seed, gid, (uint32_t)(kk >> 1), z[0], z[1]);
+            else sbr_normal_pair(seed, gid, (uint32_t)(kk >> 1), z[0], z[1], stream);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int k = kk + u;
@@ -810,6 +813,30 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_normals(SbrBuf b, uint64_t seed, 
     }
 }
 
+// Influent FUTURES without a reset (sbr_draw_influent): one lane per draw, the tables staged as the resets stage them, nothing of
+// the handle read but its first env id.  Lane t = (r * N + i) * per_env + s is draw d = first_draw + r * per_env + s of env i: the
+// reset's mix under the stream words 0 + 256 d (the normals) and 2 + 256 d (the scenario, where the caller names none), so d = 0 is
+// the reset's own draw.  The row of fourteen is what sbr_cycle_reset takes as an env's influent.
+__global__ __launch_bounds__(SBR_RESET_BLOCK) void k_draw_influent(SbrBuf b, const double* __restrict__ tables, uint64_t seed,
+                                                                  uint32_t per_env, uint32_t first_draw, uint32_t n_draws,
+                                                                  const int32_t* __restrict__ scenario, double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    stage_tables(lds, tables);
+    __syncthreads();
+    const uint32_t t = blockIdx.x * (uint32_t)SBR_RESET_BLOCK + threadIdx.x;      // n_draws < 2^31 (checked by the host)
+    if (t >= n_draws) return;
+    const uint32_t pair = t / per_env, s = t - pair * per_env, n = (uint32_t)b.n;   // pair = r * N + i
+    const uint32_t r = pair / n;
+    const int64_t i = (int64_t)(pair - r * n);
+    const uint32_t word = 256u * (first_draw + r * per_env + s);                    // d < 2^24 (checked by the host)
+    const uint64_t gid = (uint64_t)(b.first_env_id + i);
+    double ld[SBR_NX];
+    influent_lane(lds, true, scenario ? scenario[i] : sbr_scenario_draw(seed, gid, 2u + word), nullptr, nullptr, seed, gid, i, ld, word);
+    double* mine = out + (int64_t)t * SBR_NX;
+#pragma unroll
+    for (int j = 0; j < SBR_NX; ++j) mine[j] = ld[j];
+}
+
 // =========================================================================================== host / C ABI
 static thread_local std::string g_create_err;      // creation errors are reported per calling thread (sbr_last_error(NULL))
 
@@ -1033,6 +1060,7 @@ int sbr_create(int64_t n_envs, int device_id, int64_t first_env_id, const sbr_co
                               (const void*)kCycleReset<float>[carry], (const void*)kCycleReset<double>[carry]};
         for (const void* fn : fns) HIP_TRY(nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     }
+    HIP_TRY(nullptr, hipFuncSetAttribute((const void*)k_draw_influent, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     e->buf.n = n_envs; e->buf.first_env_id = first_env_id;
     *out = e.release();
     return SBR_OK;
@@ -1111,6 +1139,30 @@ int sbr_reset_carry(sbr_env* e, uint64_t seed, const int32_t* scenario, const do
 int sbr_cycle_reset(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* rnd, const double* influent,
                     const uint8_t* mask, int32_t carry_over, void* obs, void* stream) {
     return reset_impl(e, "sbr_cycle_reset", true, carry_over != 0, seed, scenario, rnd, influent, mask, obs, stream);
+}
+
+int sbr_draw_influent(sbr_env* e, uint64_t seed, int32_t rows, int32_t per_env, int32_t first_draw, const int32_t* scenario,
+                      double* out, void* stream) {
+    std::string bad;                  // every check is evaluated, the LAST failing one is reported - before anything is touched
+    if (e && !scenario && !e->cfg.random_scenario)
+        bad = "NULL scenario without cfg.random_scenario: SBROS-v1 and SBR-v2 fix different scenarios, name one";
+    if (e && !e->have_tables) bad = "sbr_set_influent_tables was never called";
+    if (rows >= 1 && per_env >= 1 && first_draw >= 0) {
+        const int64_t draws = rows * (int64_t)per_env;
+        if (e && (draws >= (int64_t)1 << 31 || e->n * draws >= (int64_t)1 << 31)) bad = "num_envs * rows * per_env must stay below 2^31 draws";
+        if (first_draw + draws > (int64_t)1 << 24) bad = "first_draw + rows * per_env must be <= 2^24 (the draw is 24 bits of the Philox stream word)";
+    }
+    if (first_draw < 0) bad = "first_draw must be >= 0";
+    if (rows < 1 || per_env < 1) bad = "rows and per_env must be >= 1";
+    if (!out) bad = "NULL out";
+    if (!e) bad = "NULL env";
+    if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_draw_influent: " + bad);
+    const int64_t n_draws = e->n * rows * (int64_t)per_env;
+    return launched(e, [&] {
+        hipLaunchKernelGGL(k_draw_influent, dim3((unsigned)((n_draws + SBR_RESET_BLOCK - 1) / SBR_RESET_BLOCK)), dim3(SBR_RESET_BLOCK),
+                           kLdsTableDoubles * sizeof(double), (hipStream_t)stream, e->buf, e->tables, seed, (uint32_t)per_env,
+                           (uint32_t)first_draw, (uint32_t)n_draws, scenario, out);
+    });
 }
 
 int sbr_set_trace(sbr_env* e, double* buf, int64_t n_envs, int64_t capacity, int32_t record_width) {

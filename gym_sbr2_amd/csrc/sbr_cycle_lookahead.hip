@@ -4,17 +4,6 @@
 //              of sbr_tape.hip through launch_branch_best)
 #include "sbr_host.h"
 
-// A lane's three set-points of a row (the wave's 64 triples are contiguous: 768 or 1536 bytes).  The compiler barrier keeps the
-// loads where they are written, as in tape_load.
-template <typename ActT>
-SBR_DEV void cycle_row_load(const ActT* row /* the workgroup's part of a row */, uint32_t l, ActT& a0, ActT& a1, ActT& a2) {
-    const ActT* mine = row + 3 * l;
-    a0 = mine[0]; a1 = mine[1]; a2 = mine[2];
-    asm volatile("" ::: "memory");
-}
-// el of the addressing (sbr_tape.hip): the env of branch j minus e0, the env of the workgroup's first branch.  <= 256; the mask
-// changes no value, it keeps a row access at scalar base + one 32-bit lane offset.
-SBR_DEV uint32_t cycle_env_of(uint32_t j, uint32_t fanout, uint32_t e0u) { return (j / fanout - e0u) & 511u; }
 // The env's stored influent, addressed like its plant: (i0, l) = (first env of the workgroup, the lane's env minus it).
 SBR_DEV void load_influent(const SbrBuf& b, int64_t i0, uint32_t l, double (&ld)[SBR_NX]) {
 #pragma unroll
@@ -119,8 +108,6 @@ SBR_CYCLE_LOOKAHEAD_TWO_WAVES(float)
 SBR_CYCLE_LOOKAHEAD_TWO_WAVES(double)
 // The branch reads the constants a second time at offset 0 of the kernel-argument segment: every build - the specialisations are
 // written out by hand - takes SbrPar by value as its FIRST parameter.  (That the host fills it from e->par is launch_fused's.)
-template <typename F> struct SbrFirstParam;
-template <typename A, typename... R> struct SbrFirstParam<void (*)(A, R...)> { using type = A; };
 #define SBR_TAKES_PAR_FIRST(...) std::is_same_v<SbrFirstParam<decltype(&k_cycle_lookahead<__VA_ARGS__>)>::type, SbrPar>
 static_assert(SBR_TAKES_PAR_FIRST(float, 1, 1) && SBR_TAKES_PAR_FIRST(double, 1, 1) && SBR_TAKES_PAR_FIRST(float, 1, 2) &&
                   SBR_TAKES_PAR_FIRST(double, 1, 2) && SBR_TAKES_PAR_FIRST(float, 0, 2) && SBR_TAKES_PAR_FIRST(double, 0, 2),

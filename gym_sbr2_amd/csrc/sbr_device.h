@@ -1217,9 +1217,10 @@ SBR_DEV double sbr_u53(uint32_t hi, uint32_t lo) {     // uniform in (0, 1]
     return ((double)v + 1.0) * (1.0 / 9007199254740992.0);
 }
 
-// two standard normals: Box-Muller on Philox block i of stream 0
-SBR_DEV void sbr_normal_pair(uint64_t seed, uint64_t env_id, uint32_t i, double& z0, double& z1) {
-    uint32_t c[4] = {i, 0u, (uint32_t)env_id, (uint32_t)(env_id >> 32)};
+// two standard normals: Box-Muller on Philox block i of stream 0.  `stream` is the stream word: 0 + 256 * d for draw d of
+// sbr_draw_influent (the draw index in the upper 24 bits, as the sampler and the policy noise carry their branch index)
+SBR_DEV void sbr_normal_pair(uint64_t seed, uint64_t env_id, uint32_t i, double& z0, double& z1, uint32_t stream = 0u) {
+    uint32_t c[4] = {i, stream, (uint32_t)env_id, (uint32_t)(env_id >> 32)};
     sbr_philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     const double u1 = sbr_u53(c[0], c[1]), u2 = sbr_u53(c[2], c[3]);
     const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925286766559 * u2;

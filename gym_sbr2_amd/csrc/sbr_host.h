@@ -109,14 +109,18 @@ template <typename F> static void dispatch(const sbr_env* e, F&& f) {
 template <int SCH> constexpr int kFusedOneWave = SCH == 1 ? 1 : 2;
 // The launch of a fused kernel over `lanes` lanes: the handle's envs, or the branches of a lookahead - the register budget goes by
 // the lanes of THE launch.  kernel(w) names the build for decltype(w)::value waves per SIMD; e->par and e->buf lead its arguments.
-// That order is relied on: k_cycle_lookahead reads SbrPar a second time at offset 0 of its kernel-argument segment
-// (sbr_cycle_lookahead.hip, which asserts the first parameter of each of its builds).
+// That order is relied on: k_cycle_lookahead and k_cycle_lookahead_scenarios read SbrPar a second time at offset 0 of their
+// kernel-argument segment (sbr_cycle_lookahead.hip, sbr_cycle_scenarios.hip: each asserts the first parameter of its builds).
 template <int SCH, typename Kernel, typename... Args>
 static void launch_fused(const sbr_env* e, int64_t lanes, void* stream, Kernel&& kernel, Args... args) {
     const auto fn = fused_waves_for(e, lanes) == 1 ? kernel(std::integral_constant<int, kFusedOneWave<SCH>>{})
                                                    : kernel(std::integral_constant<int, 2>{});
     hipLaunchKernelGGL(fn, grid_for(lanes), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, args...);
 }
+
+// the type of a kernel's first parameter, for the units that assert the order launch_fused relies on
+template <typename F> struct SbrFirstParam;
+template <typename A, typename... R> struct SbrFirstParam<void (*)(A, R...)> { using type = A; };
 
 // Argument checks that several families share, and the one kernel two of them launch without owning it: defined in
 // sbr_tape.hip, which owns k_branch_best.

@@ -209,6 +209,19 @@ SBR_DEV void tape_load(const ActT* row /* the workgroup's part of a row */, uint
     a0 = v.x; a1 = v.y;
 }
 
+// The per-cycle lookaheads (sbr_cycle_lookahead.hip, sbr_cycle_scenarios.hip).  A lane's three set-points of a row (a wave's 64
+// triples are contiguous where its lanes' rows are: 768 or 1536 bytes).  The compiler barrier keeps the loads where they are
+// written, as in tape_load.
+template <typename ActT>
+SBR_DEV void cycle_row_load(const ActT* row /* the workgroup's part of a row */, uint32_t l, ActT& a0, ActT& a1, ActT& a2) {
+    const ActT* mine = row + 3 * l;
+    a0 = mine[0]; a1 = mine[1]; a2 = mine[2];
+    asm volatile("" ::: "memory");
+}
+// el of the addressing (sbr_tape.hip): the env of branch j minus e0, the env of the workgroup's first branch, an env holding
+// `fanout` consecutive branches.  <= 256; the mask changes no value, it keeps a row access at scalar base + one 32-bit lane offset.
+SBR_DEV uint32_t cycle_env_of(uint32_t j, uint32_t fanout, uint32_t e0u) { return (j / fanout - e0u) & 511u; }
+
 // Where a branch ENDED (sbr_lookahead_actions_end / sbr_lookahead_sampled_end), for a terminal value on top of its return: stored
 // once per launch and branch, behind the loop.  Each output is optional (wave-uniform tests).  A branch that is not done: the
 // rows k_step forms for a call that does not end the episode - sbr_write_obs / sbr_write_state of the plant, the last interval's

@@ -10,7 +10,7 @@ from .vec_env import SbrOSVec, _ptr
 
 
 class CycleLookahead:
-    """SBR-v2's own fused call, mixed into SbrEnv2Vec (whose class body is reset, step and the refusals and nothing else)."""
+    """SBR-v2's own fused calls, mixed into SbrEnv2Vec (whose class body is reset, step and the refusals and nothing else)."""
 
     # the per-branch rows of the last cycle: obs_end, diag_end, status (see _fanout_outputs)
     _CYCLE_END_ROWS = (((_capi.NCYC_OBS,), torch.float64), ((_capi.NCYC_DIAG,), torch.float64), ((), torch.uint8))
@@ -39,6 +39,60 @@ class CycleLookahead:
                                                        (return_end, return_end, return_status), end_rows=self._CYCLE_END_ROWS)
         _capi.check(self.lib.sbr_cycle_lookahead(self._h, n_cycles, fanout, _ptr(a) if n_cycles else None, *ptrs, *end_ptrs,
                                                  self._stream()), self._h)
+        return results
+
+    def draw_influent(self, rows, per_env, seed=0, scenario=None, first_draw=0):
+        """Influent FUTURES without a reset (sbr_draw_influent): [rows, N, per_env, 14] float64, rows x per_env draws of the
+        reset's influent mix per env; a row of 14 is what reset(influent=...) takes for one env.  Draw (r, i, s) has index
+        d = first_draw + r*per_env + s and depends on (seed, the env's global id, d, its scenario) and on nothing else; d = 0 is
+        the draw of reset(seed).  `scenario` [N] int32 is shared by an env's draws; None: drawn per draw on the device under
+        cfg.random_scenario, otherwise scenario 0 (SbrEnv2's fixed one).  Nothing of the handle is written."""
+        rows, per_env = int(rows), int(per_env)
+        if rows < 1 or per_env < 1 or self.num_envs * rows * per_env >= 2 ** 31:      # before the output is sized by it
+            raise ValueError("rows and per_env must be >= 1 with num_envs * rows * per_env below 2^31")
+        if scenario is None and not self.cfg.random_scenario:
+            scenario = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
+        scen = self._keep = self._dev(scenario, torch.int32, (self.num_envs,))
+        out = torch.empty((rows, self.num_envs, per_env, _capi.NX), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.sbr_draw_influent(self._h, C.c_uint64(int(seed)), rows, per_env, int(first_draw), _ptr(scen),
+                                                   _ptr(out), self._stream()), self._h)
+        return out
+
+    def influent_futures(self, n_cycles, n_scen, seed=0, scenario=None, first_draw=0, current_first=True):
+        """The `influent` of cycle_lookahead_scenarios, [n_cycles, N, n_scen, 14]: draw_influent(n_cycles, n_scen, ...), with
+        current_first the first cycle of every future under the influent the handle holds - the cycle about to start is the one
+        whose influent is known."""
+        out = self.draw_influent(n_cycles, n_scen, seed, scenario, first_draw)
+        if current_first:
+            out[0] = self.influent().T[:, None, :]
+        return out
+
+    def cycle_lookahead_scenarios(self, candidates, influent, return_rewards=False, return_stats=False, return_best=False,
+                                  return_end=False, return_status=False):
+        """cycle_lookahead under UNCERTAIN influent, one launch (sbr_cycle_lookahead_scenarios): `candidates` is
+        [n_cycles, N, K, 3] as for cycle_lookahead, `influent` [n_cycles, N, S, 14] float64 (draw_influent's layout) - S futures
+        per env, and every candidate of an env is played against the same S (common random numbers).  Cycle c of branch
+        (i, k, s) runs under influent[c, i, s]; the handle's stored influent is never read (influent_futures puts it into
+        cycle 0) and the handle is left bit for bit as it was.  Returns the sum of the cycles' rewards per branch [N, K, S]
+        float64, then, in this order and only if asked for: the reward of every cycle [n_cycles, N, K, S]; mean and worst
+        [N, K], the mean over s (summed in s order, one division) and the smallest of a candidate's S returns, NaN if one of
+        them is; best_index [N] int32 and best_value [N] float64, the winner among an env's means (cycle_lookahead's rule);
+        obs_end [N, K, S, 3] and diag_end [N, K, S, 12] float64; status [N, K, S] uint8 - all as cycle_lookahead gives them."""
+        shape, ishape = tuple(getattr(candidates, "shape", ())), tuple(getattr(influent, "shape", ()))
+        if not (len(shape) == 4 and shape[1] == self.num_envs and shape[2] >= 1 and shape[3] == _capi.NCYC_ACT):
+            raise ValueError("candidates must have shape [n_cycles,N,K,3] with K >= 1")
+        if not (len(ishape) == 4 and ishape[:2] == shape[:2] and ishape[2] >= 1 and ishape[3] == _capi.NX):
+            raise ValueError("influent must have shape [n_cycles,N,S,14] with S >= 1 and candidates' n_cycles")
+        n_cycles, fanout, n_scen = int(shape[0]), int(shape[2]), int(ishape[2])
+        if self.num_envs * fanout * n_scen >= 2 ** 31:           # before the outputs are sized by it
+            raise ValueError("num_envs * K * S must stay below 2^31")
+        a, f = self._keep_a = (self._as_actions(candidates, shape), self._dev(influent, torch.float64, ishape))
+        ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_cycles, 1, return_rewards, return_best,
+                                                       (return_end, return_end, return_status), end_rows=self._CYCLE_END_ROWS,
+                                                       n_scen=n_scen, return_stats=return_stats)
+        _capi.check(self.lib.sbr_cycle_lookahead_scenarios(self._h, n_cycles, fanout, n_scen, _ptr(a) if n_cycles else None,
+                                                           _ptr(f) if n_cycles else None, *ptrs, *end_ptrs, self._stream()), self._h)
         return results
 
 

@@ -3,9 +3,11 @@ policy-rollout planner on the closed-loop lookahead.
 
 Plumbing only: the candidates are drawn, scored and averaged inside libsbr_amd.so (sbr_lookahead_sampled, sbr_mppi_update,
 sbr_lookahead_policy); nothing here does arithmetic on a candidate.  The sums formed here add the caller's terminal value to a
-return and average an env's returns.  The exception is CycleSetpointSearch for the per-cycle env SBR-v2: its candidates are
-three numbers per cycle, drawn and refitted in torch, and scored by sbr_cycle_lookahead."""
+return and average an env's returns.  The exception is CycleSetpointSearch for the per-cycle env SBR-v2, and
+RobustCycleSetpointSearch on top of it: their candidates are three numbers per cycle, drawn and refitted in torch, and scored by
+sbr_cycle_lookahead or, over influent futures, by sbr_cycle_lookahead_scenarios."""
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -131,7 +133,7 @@ class CycleSetpointSearch:
             cand = (mean + std * torch.randn(shape, generator=gen, dtype=torch.float64, device=env.device)).clamp_(0.0, 1.0)
             cand[:, :, :1] = best
             cand = cand.to(env.action_dtype).double()            # the values the kernel integrates
-            ret, status = env.cycle_lookahead(cand, return_status=True)
+            ret, status = self._score(cand)
             out = ((status & bad_bits) != 0) | ret.isnan()
             top, idx = ret.masked_fill(out, float("-inf")).topk(self.n_elite, dim=1)
             ok = top > float("-inf")                             # [N, n_elite]: the elite is a candidate that may win
@@ -147,6 +149,43 @@ class CycleSetpointSearch:
         self.tape, self.status = best[:, :, 0], flags
         self.decision += 1
         return self.tape[0].to(env.action_dtype), value
+
+    def _score(self, cand):
+        """What the loop ranks the candidates [n_cycles, N, K, 3] by: (value [N, K] float64, status bits [N, K] uint8)."""
+        return self.env.cycle_lookahead(cand, return_status=True)
+
+
+class RobustCycleSetpointSearch(CycleSetpointSearch):
+    """CycleSetpointSearch when the influent of the coming cycles is NOT known: the same cross-entropy loop, every candidate
+    scored over `n_scen` influent futures - the same futures for all candidates of an env (cycle_lookahead_scenarios), so that two
+    tapes differ by what they do and not by what they drew.  risk="mean" ranks a candidate by the mean of its n_scen returns,
+    risk="worst" by the smallest of them.  One set of futures per plan(): env.influent_futures(n_cycles, n_scen, seed,
+    first_draw = 1 + plans so far * n_cycles * n_scen) - cycle 0 under the influent the handle holds, later cycles drawn, no
+    draw used twice and none the draw of reset(seed).  A candidate is left out of the fit and cannot win if ANY of its n_scen
+    branches came near a pole or went non-finite; `status` [N] is the OR of the winner's branches' bits.  After plan(): `tape`,
+    `status` as CycleSetpointSearch keeps them and `futures` [n_cycles, N, n_scen, 14]; the returned value is exactly
+    cycle_lookahead_scenarios' mean (or worst) of `tape` on `futures`.
+
+        search = RobustCycleSetpointSearch(env, K=64, n_scen=16, n_cycles=3, risk="worst")
+        action, value = search.plan(); env.step(action); env.reset(influent=..., carry_over=True)
+    """
+
+    def __init__(self, env, K, n_scen, n_cycles=2, iters=3, elite_frac=0.25, seed=0, risk="mean"):
+        super().__init__(env, K, n_cycles, iters, elite_frac, seed)
+        self.n_scen, self.risk, self.futures = int(n_scen), risk, None
+        if self.n_scen < 1:
+            raise ValueError("n_scen must be >= 1")
+        if risk not in ("mean", "worst"):
+            raise ValueError('risk must be "mean" or "worst"')
+
+    def plan(self):
+        self.futures = self.env.influent_futures(self.n_cycles, self.n_scen, seed=self.seed,
+                                                 first_draw=1 + self.decision * self.n_cycles * self.n_scen)
+        return super().plan()
+
+    def _score(self, cand):
+        _, mean, worst, status = self.env.cycle_lookahead_scenarios(cand, self.futures, return_stats=True, return_status=True)
+        return (mean if self.risk == "mean" else worst), functools.reduce(lambda u, v: u | v, status.unbind(-1))
 
 
 class PolicyRolloutPlanner:

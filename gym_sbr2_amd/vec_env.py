@@ -299,26 +299,31 @@ class SbrOSVec:
     _END_ROWS = (((_capi.NOBS,), torch.float32), ((_capi.NSTATE,), torch.float32), ((), torch.bool))
 
     def _fanout_outputs(self, fanout, n_steps, hold, return_rewards, return_best, return_end, return_actions=False,
-                        actions_dtype=None, end_rows=_END_ROWS):
+                        actions_dtype=None, end_rows=_END_ROWS, n_scen=None, return_stats=False):
         """What a fan-out launch writes, sized once for lookahead, lookahead_sampled and lookahead_policy (and their _end forms)
-        and for SBR-v2's cycle_lookahead.  Returns (ptrs, end_ptrs, results).  `ptrs` is in the ABI's order: returns, rewards,
-        best_index, best_return and - only for a call that has the output at all, actions_dtype not None - actions; `end_ptrs`
-        is one pointer per entry of `end_rows` (obs_end, state_end, done_end unless the caller names its own); return_end is
-        one flag for all of them or one per entry.  An output that was not asked for is a None pointer.  `results` is what the
-        method returns, in the one public order: returns, rewards, best_index, best_return, actions, then the end rows - those
-        asked for."""
+        and for SBR-v2's cycle_lookahead and cycle_lookahead_scenarios.  Returns (ptrs, end_ptrs, results).  `ptrs` is in the
+        ABI's order: returns, rewards, best_index, best_return and - only for a call that has the output at all, actions_dtype
+        not None - actions; `end_ptrs` is one pointer per entry of `end_rows` (obs_end, state_end, done_end unless the caller
+        names its own); return_end is one flag for all of them or one per entry.  An output that was not asked for is a None
+        pointer.  `results` is what the method returns, in the one public order: returns, rewards, best_index, best_return,
+        actions, then the end rows - those asked for.  n_scen (cycle_lookahead_scenarios): a branch is (env, candidate, future),
+        so the per-branch outputs gain a trailing axis of n_scen, and mean and worst [N, K] follow the rewards in both orders;
+        the winners are reduced from the means, so return_best sizes mean too."""
         n, dev = self.num_envs, self.device
-        ret = torch.empty((n, fanout), dtype=torch.float64, device=dev)
-        rew = torch.empty((n_steps, n, fanout), dtype=torch.float64, device=dev) if return_rewards else None
+        per = (n, fanout) if n_scen is None else (n, fanout, n_scen)
+        ret = torch.empty(per, dtype=torch.float64, device=dev)
+        rew = torch.empty((n_steps,) + per, dtype=torch.float64, device=dev) if return_rewards else None
+        stats = () if n_scen is None else tuple(torch.empty((n, fanout), dtype=torch.float64, device=dev) if w else None
+                                                for w in (return_stats or return_best, return_stats))
         bi = torch.empty((n,), dtype=torch.int32, device=dev) if return_best else None
         br = torch.empty((n,), dtype=torch.float64, device=dev) if return_best else None
         acts = torch.empty((-(-n_steps // hold), n, fanout, 2), dtype=actions_dtype, device=dev) if return_actions else None
         wanted = return_end if isinstance(return_end, (tuple, list)) else (return_end,) * len(end_rows)
-        ends = tuple(torch.empty((n, fanout) + trailing, dtype=dtype, device=dev) if w else None
+        ends = tuple(torch.empty(per + trailing, dtype=dtype, device=dev) if w else None
                      for (trailing, dtype), w in zip(end_rows, wanted))
-        outs = (ret, rew, bi, br) + ((acts,) if actions_dtype is not None else ())
+        outs = (ret, rew) + stats + (bi, br) + ((acts,) if actions_dtype is not None else ())
         return ([_ptr(t) for t in outs], [_ptr(t) for t in ends],
-                _one_or_all(tuple(t for t in (ret, rew, bi, br, acts) + ends if t is not None)))
+                _one_or_all(tuple(t for t in (ret, rew) + (stats if return_stats else ()) + (bi, br, acts) + ends if t is not None)))
 
     def _lookahead(self, actions, n_steps, hold, return_rewards, return_best, end):
         hold = int(hold)

@@ -310,6 +310,37 @@ int sbr_cycle_lookahead(sbr_env* env, int32_t n_cycles, int32_t fanout, const vo
                         double* returns, double* rewards_out, int32_t* best_index, double* best_return,
                         double* obs_end, double* diag_end, uint8_t* status_out, void* stream);
 
+/* sbr_cycle_lookahead under UNCERTAIN influent: `fanout` candidate tapes per env, each played against `n_scen` influent futures -
+ * the SAME n_scen futures for every candidate of an env (common random numbers), so that candidates are compared on futures and
+ * not on noise.  sbr_cycle_lookahead plays every later cycle under the influent the env was last reset with, the one thing an
+ * operator does not know; here every cycle of every future has an influent of its own, and the env's STORED influent is never read.
+ * A BRANCH is j = (i*fanout + k)*n_scen + s: env i, candidate k, future s; there are B = N*fanout*n_scen < 2^31 of them.
+ *   actions     [n_cycles][N*fanout][3] ActT, DEVICE pointer: sbr_cycle_lookahead's tape, not expanded over s
+ *   influent    [n_cycles][N*n_scen][SBR_NX] float64, DEVICE pointer: sbr_draw_influent's layout, not expanded over k.  Cycle c of
+ *               branch j runs under entries 1..13 of influent[c][i*n_scen + s] and forms entry 0 from its own volume - what
+ *               sbr_cycle_reset(carry_over = 1, influent = that row) followed by sbr_cycle_step computes, with the same bits in
+ *               every output.  A caller who wants cycle 0 under the influent the env holds puts it into row 0.
+ *   returns     [B] float64 or NULL: sum of the branch's rewards, added in cycle order from 0.0
+ *   rewards_out [n_cycles][B] float64 or NULL: the reward of every cycle
+ *   mean_out    [N*fanout] float64 or NULL: ((..(0.0 + r_0) + r_1 ..) + r_{S-1}) / (double)S over the candidate's n_scen returns in
+ *               s order, one IEEE division; a NaN propagates
+ *   worst_out   [N*fanout] float64 or NULL: the smallest of the candidate's n_scen returns, NaN if any of them is NaN.  Both are
+ *               reduced FROM `returns` by a second kernel on the same stream: give returns with them
+ *   best_index  [N] int32 or NULL, best_value [N] float64 or NULL: the winner among each env's `fanout` entries of mean_out under
+ *               the rule of sbr_lookahead_actions, reduced FROM `mean_out`: give mean_out with them (a caller who plans for the
+ *               worst case passes worst_out to sbr_branch_best)
+ *   obs_end [B][SBR_NCYC_OBS], diag_end [B][SBR_NCYC_DIAG] float64, status_out [B] uint8, each or NULL: as in sbr_cycle_lookahead
+ * NOTHING of the handle is written and nothing is allocated (graph-capturable).  The register budget of the launch goes by B.
+ * n_cycles = 0 writes returns = mean_out = worst_out = 0, best_index = 0 and best_value = 0 and reads nothing.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): NULL env; n_cycles < 0; n_scen < 1;
+ * fanout < 1; N*fanout*n_scen >= 2^31; actions or influent NULL with n_cycles > 0; obs_end, diag_end or status_out given with
+ * n_cycles = 0; mean_out or worst_out given while returns is NULL; best_index or best_value given while mean_out is NULL. */
+int sbr_cycle_lookahead_scenarios(sbr_env* env, int32_t n_cycles, int32_t fanout, int32_t n_scen,
+                                  const void* actions, const double* influent,
+                                  double* returns, double* rewards_out, double* mean_out, double* worst_out,
+                                  int32_t* best_index, double* best_value,
+                                  double* obs_end, double* diag_end, uint8_t* status_out, void* stream);
+
 /* fused rollout with an on-device uniform random policy (BASELINE.json configs[4]): n_steps step()
  * calls per env in ONE kernel, plant state held in registers; actions ~ U[0,act_DO_max] x
  * U[0,act_EC_max] from Philox keyed by policy_seed, subsequence = global env id, counter = call index.
@@ -607,6 +638,25 @@ int sbr_draw_normals(sbr_env* env, uint64_t seed, double* out, void* stream);
 /* the scenario each env gets from sbr_reset(seed, scenario = NULL) when cfg.random_scenario = 1: out [N] int32, DEVICE
  * pointer (replaces np.random.choice(8, 1), gym_SBR_env4.py:107). */
 int sbr_draw_scenarios(sbr_env* env, uint64_t seed, int32_t* out, void* stream);
+
+/* influent FUTURES without a reset: `rows` x `per_env` draws of the reset's influent mix per env (scenario tables + 48 normals,
+ * buffer_tank3.py:68-107), nothing of the handle written, nothing allocated (graph-capturable).
+ *   out      [rows][N][per_env][SBR_NX] float64, DEVICE pointer.  A row of 14 is what sbr_cycle_reset takes as one env's `influent`
+ *            and what sbr_get_influent returns for it: entries 1..13 the flow-weighted means, entry 0 the 0.66 of
+ *            buffer_tank3.py:107 (no consumer reads it).  out[c] is one cycle's `influent` of sbr_cycle_lookahead_scenarios with
+ *            n_scen = per_env.
+ *   draw (r, i, s) has index d = first_draw + r*per_env + s.  Its 48 normals are the Box-Muller pairs of Philox4x32-10 under key
+ *            `seed` at counters (pair 0..23, 0 + 256*d, g_lo, g_hi), g the GLOBAL env id: the draw index in the upper 24 bits of
+ *            the stream word.  d = 0 is exactly the draw of sbr_reset / sbr_cycle_reset(seed, rnd = NULL).  A draw depends on
+ *            (seed, g, d, scenario) and on nothing else - not on N, rows, per_env or the shard.
+ *   scenario [N] int32 or NULL, shared by an env's draws.  NULL with cfg.random_scenario = 1: draw d takes Philox block
+ *            (0, 2 + 256*d, g_lo, g_hi) under `seed` (d = 0: sbr_draw_scenarios' value).  NULL with cfg.random_scenario = 0 is
+ *            refused: sbr_reset and sbr_cycle_reset fix different scenarios, so the caller names one.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): NULL env or out; rows < 1 or per_env < 1;
+ * first_draw < 0; first_draw + rows*per_env > 2^24; N*rows*per_env >= 2^31; sbr_set_influent_tables never called; NULL scenario
+ * without cfg.random_scenario. */
+int sbr_draw_influent(sbr_env* env, uint64_t seed, int32_t rows, int32_t per_env, int32_t first_draw,
+                      const int32_t* scenario, double* out, void* stream);
 
 /* Block the calling host thread until everything queued on `stream` has finished (hipStreamSynchronize on the handle's
  * device).  For host-driven callers: the reference's step() returns finished numbers, so the reference-shaped single env
