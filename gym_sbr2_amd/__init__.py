@@ -44,6 +44,9 @@ def __getattr__(name):          # torch is imported only when the env classes ar
     if name == "MlpPolicy":
         from .policy import MlpPolicy
         return MlpPolicy
+    if name == "PlantModels":
+        from .models import PlantModels
+        return PlantModels
     if name in ("TapeSampler", "MppiPlanner", "PolicyRolloutPlanner", "CycleSetpointSearch", "RobustCycleSetpointSearch"):
         from . import planner
         return getattr(planner, name)

@@ -86,6 +86,10 @@ SYMBOLS = {
     "sbr_cycle_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_cycle_lookahead": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_cycle_lookahead_scenarios": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_check_model": (C.c_int, [C.POINTER(SbrConfig), C.POINTER(SbrConfig)]),
+    "sbr_set_models": (C.c_int, [_VP, _I32, C.POINTER(SbrConfig)]),
+    "sbr_num_models": (_I64, [_VP]),
+    "sbr_cycle_lookahead_models": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_rollout": (C.c_int, [_VP, _I32, _U64, _VP, _VP, _VP]),
     "sbr_rollout_actions": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_actions": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),

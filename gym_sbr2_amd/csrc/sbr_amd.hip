@@ -9,3 +9,4 @@
 #include "sbr_policy_collect.hip"
 #include "sbr_cycle_lookahead.hip"
 #include "sbr_cycle_scenarios.hip"
+#include "sbr_cycle_models.hip"

@@ -858,7 +858,7 @@ static double rows_threshold(double dt, int rows) {
     return s;
 }
 
-static void derive_params(const sbr_config& c, SbrPar& p) {
+void derive_params(const sbr_config& c, SbrPar& p) {
     p.muH = c.muH; p.Ks = c.Ks; p.Koh = c.Koh; p.Kno = c.Kno; p.bH = c.bH; p.eta_g = c.eta_g; p.eta_h = c.eta_h;
     p.kh = c.kh; p.Kx = c.Kx; p.muA = c.muA; p.Knh = c.Knh; p.bA = c.bA; p.Koa = c.Koa; p.ka = c.ka;
     const double Yh = c.Yh, Ya = c.Ya, ixb = c.ixb, ixp = c.ixp, fp = c.fp;
@@ -932,7 +932,7 @@ template <typename T, int BLK> constexpr ResetFn<T> kReset[2] = {k_reset<T, fals
 template <typename T> constexpr ResetFn<T> kCycleReset[2] = {k_cycle_reset<T, false>, k_cycle_reset<T, true>};
 
 // What sbr_create has to say about a config; empty if it is valid.  Every check is evaluated and the LAST failing one is reported.
-static std::string config_error(const sbr_config& c) {
+std::string config_error(const sbr_config& c) {
     std::string bad;
     if (c.substeps < 1 || c.substeps > 10000) bad = "substeps out of range";
     if (c.scheme < 0 || c.scheme > 1) bad = "scheme must be 0 (RK4 x substeps) or 1 (adaptive Butcher-5)";
@@ -1073,6 +1073,7 @@ int sbr_destroy(sbr_env* e) {
     if (e->buf.ctrl) (void)hipFree(e->buf.ctrl);
     if (e->buf.infl) (void)hipFree(e->buf.infl);
     if (e->tables) (void)hipFree(e->tables);
+    if (e->models) (void)hipFree(e->models);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     delete e;

@@ -125,6 +125,14 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_scenario_stats(const double* __re
     if (worst_out) worst_out[m] = worst;
 }
 
+// k_scenario_stats for the unit that shares it (sbr_cycle_models.hip): a kernel is named in one unit only.  Nothing is launched
+// when neither output was asked for.
+void launch_scenario_stats(const double* returns, int64_t n_pairs, int32_t n_scen, double* mean_out, double* worst_out, void* stream) {
+    if (mean_out || worst_out)
+        hipLaunchKernelGGL(k_scenario_stats, grid_for(n_pairs), dim3(SBR_BLOCK), 0, (hipStream_t)stream, returns, n_pairs,
+                           (uint32_t)n_scen, mean_out, worst_out);
+}
+
 extern "C" {
 
 int sbr_cycle_lookahead_scenarios(sbr_env* e, int32_t n_cycles, int32_t fanout, int32_t n_scen, const void* actions,

@@ -24,9 +24,16 @@ struct sbr_env {
     double* tables = nullptr;     // [2][8][14][48] on the device
     int64_t one_wave_envs = 65536; // lanes of one wave per SIMD on this device: CUs x 4 SIMDs x 64 (MI355X: 256 CUs)
     bool have_tables = false;
+    SbrPar* models = nullptr;     // [n_models] on the device: the plant models of sbr_set_models (sbr_cycle_models.hip), or none
+    int64_t n_models = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
 };
+
+// A config folded into the constants the kernels read, and what sbr_create has to say about a config (empty if it is valid):
+// defined in sbr_core.hip, shared with sbr_set_models / sbr_check_model (sbr_cycle_models.hip).
+SBR_INTERNAL void derive_params(const sbr_config& c, SbrPar& p);
+SBR_INTERNAL std::string config_error(const sbr_config& c);
 
 // Defined once, in sbr_core.hip, next to the calling thread's error text it writes when there is no handle (sbr_last_error(NULL)):
 // a copy per unit would each keep a text of its own.
@@ -118,6 +125,17 @@ static void launch_fused(const sbr_env* e, int64_t lanes, void* stream, Kernel&&
     hipLaunchKernelGGL(fn, grid_for(lanes), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, args...);
 }
 
+// launch_fused on a two-dimensional grid, for the one kernel that reads its constants from the handle's model table and not from
+// e->par (k_cycle_lookahead_models, sbr_cycle_models.hip): lanes_x lanes along x, rows_y <= 65535 rows along y, the register
+// budget by their product.  e->models, e->n_models and e->buf lead the arguments.
+template <int SCH, typename Kernel, typename... Args>
+static void launch_fused_models(const sbr_env* e, int64_t lanes_x, int32_t rows_y, void* stream, Kernel&& kernel, Args... args) {
+    const auto fn = fused_waves_for(e, lanes_x * rows_y) == 1 ? kernel(std::integral_constant<int, kFusedOneWave<SCH>>{})
+                                                              : kernel(std::integral_constant<int, 2>{});
+    hipLaunchKernelGGL(fn, dim3(grid_for(lanes_x).x, (unsigned)rows_y), dim3(SBR_BLOCK), 0, (hipStream_t)stream,
+                       (const SbrPar*)e->models, (uint32_t)e->n_models, e->buf, args...);
+}
+
 // the type of a kernel's first parameter, for the units that assert the order launch_fused relies on
 template <typename F> struct SbrFirstParam;
 template <typename A, typename... R> struct SbrFirstParam<void (*)(A, R...)> { using type = A; };
@@ -129,3 +147,6 @@ SBR_INTERNAL void best_error(std::string& bad, const double* returns, const int3
 SBR_INTERNAL std::string end_error(int32_t n_steps, const void* obs_end, const void* state_end, const void* done_end);
 SBR_INTERNAL void launch_branch_best(const sbr_env* e, int32_t fanout, const double* values, int32_t* best_index, double* best_value,
                                      void* stream);
+// k_scenario_stats for a caller outside its unit (sbr_cycle_scenarios.hip owns it): mean and worst of each pair's n_scen returns
+SBR_INTERNAL void launch_scenario_stats(const double* returns, int64_t n_pairs, int32_t n_scen, double* mean_out, double* worst_out,
+                                        void* stream);

@@ -95,6 +95,62 @@ class CycleLookahead:
                                                            _ptr(f) if n_cycles else None, *ptrs, *end_ptrs, self._stream()), self._h)
         return results
 
+    def set_models(self, models):
+        """The handle's table of plant MODELS (sbr_set_models): `models` is a models.PlantModels or a sequence of _capi.SbrConfig
+        that differ from the env's config in the model fields only (models.MODEL_FIELDS); None or an empty sequence drops the
+        table.  Replaces an earlier table, waiting for the device first.  reset(), step() and every other call keep
+        integrating the env's own config."""
+        from .models import PlantModels
+        if models is not None and not isinstance(models, PlantModels):
+            models = PlantModels(models, base=self.cfg) if len(models) else None
+        n = 0 if models is None else len(models)
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.sbr_set_models(self._h, n, models.c_array() if n else None), self._h)
+
+    @property
+    def num_models(self):
+        """Models in the handle's table (sbr_num_models); 0 if none is set."""
+        return int(self.lib.sbr_num_models(self._h))
+
+    def cycle_lookahead_models(self, candidates, influent=None, n_scen=None, return_rewards=False, return_stats=False,
+                               return_best=False, return_end=False, return_status=False):
+        """cycle_lookahead_scenarios under UNCERTAIN PLANT KINETICS, one launch (sbr_cycle_lookahead_models): future s of every env
+        runs under MODEL s % num_models of the table set_models() gave the handle, in every cycle - the env's own config is not
+        integrated by any branch (put it into the table to have the nominal plant among the futures).  `candidates` is
+        [n_cycles, N, K, 3]; `influent` [n_cycles, N, S, 14] as for cycle_lookahead_scenarios, so that a future is an influent
+        AND a plant, or None: every cycle of every future then runs under the env's stored influent (cycle_lookahead's rule)
+        and the futures differ by their model alone.  n_scen = S defaults to influent's S, or to num_models without influent; with
+        both given they must agree.  At most 65535 futures.  The handle is left bit for bit as it was.  Results and their order
+        are cycle_lookahead_scenarios': returns [N, K, S], then if asked for the rewards [n_cycles, N, K, S], mean and worst
+        [N, K], best_index and best_value [N], obs_end [N, K, S, 3] and diag_end [N, K, S, 12], status [N, K, S]."""
+        shape = tuple(getattr(candidates, "shape", ()))
+        if not (len(shape) == 4 and shape[1] == self.num_envs and shape[2] >= 1 and shape[3] == _capi.NCYC_ACT):
+            raise ValueError("candidates must have shape [n_cycles,N,K,3] with K >= 1")
+        if influent is not None:
+            ishape = tuple(getattr(influent, "shape", ()))
+            if not (len(ishape) == 4 and ishape[:2] == shape[:2] and ishape[2] >= 1 and ishape[3] == _capi.NX):
+                raise ValueError("influent must have shape [n_cycles,N,S,14] with S >= 1 and candidates' n_cycles")
+            if n_scen is not None and int(n_scen) != ishape[2]:
+                raise ValueError("n_scen must be influent's S when both are given")
+            n_scen = int(ishape[2])
+        else:
+            n_scen = self.num_models if n_scen is None else int(n_scen)
+        if not 1 <= n_scen <= 65535:
+            raise ValueError("n_scen must be in 1 .. 65535 (without influent and n_scen it is num_models: call set_models first)")
+        n_cycles, fanout = int(shape[0]), int(shape[2])
+        if self.num_envs * fanout * n_scen >= 2 ** 31:           # before the outputs are sized by it
+            raise ValueError("num_envs * K * S must stay below 2^31")
+        a = self._as_actions(candidates, shape)
+        f = None if influent is None else self._dev(influent, torch.float64, ishape)
+        self._keep_a = (a, f)
+        ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_cycles, 1, return_rewards, return_best,
+                                                       (return_end, return_end, return_status), end_rows=self._CYCLE_END_ROWS,
+                                                       n_scen=n_scen, return_stats=return_stats)
+        _capi.check(self.lib.sbr_cycle_lookahead_models(self._h, n_cycles, fanout, n_scen, _ptr(a) if n_cycles else None,
+                                                        _ptr(f) if n_cycles and f is not None else None, *ptrs, *end_ptrs,
+                                                        self._stream()), self._h)
+        return results
+
 
 class SbrEnv2Vec(CycleLookahead, SbrOSVec):
     """N SBR-v2 environments.  reset() -> obs [N,3]; step(a [N,3] in [0,1]) -> obs [N,3], reward [N], done (all True).

@@ -168,7 +168,14 @@ class RobustCycleSetpointSearch(CycleSetpointSearch):
 
         search = RobustCycleSetpointSearch(env, K=64, n_scen=16, n_cycles=3, risk="worst")
         action, value = search.plan(); env.step(action); env.reset(influent=..., carry_over=True)
+
+    UNCERTAIN PLANT KINETICS as well: assign `search.plant_models = True` on an env that holds a model table (env.set_models(...)).
+    The candidates are then scored with cycle_lookahead_models on the same futures, and each future is an influent AND a plant:
+    future s runs under model s % env.num_models, so n_scen a multiple of num_models gives every model the same number of
+    influents.  The returned value is then cycle_lookahead_models' mean (or worst) of `tape` on `futures`.  False (the default):
+    every future runs under the env's own config.
     """
+    plant_models = False
 
     def __init__(self, env, K, n_scen, n_cycles=2, iters=3, elite_frac=0.25, seed=0, risk="mean"):
         super().__init__(env, K, n_cycles, iters, elite_frac, seed)
@@ -184,7 +191,8 @@ class RobustCycleSetpointSearch(CycleSetpointSearch):
         return super().plan()
 
     def _score(self, cand):
-        _, mean, worst, status = self.env.cycle_lookahead_scenarios(cand, self.futures, return_stats=True, return_status=True)
+        look = self.env.cycle_lookahead_models if self.plant_models else self.env.cycle_lookahead_scenarios
+        _, mean, worst, status = look(cand, self.futures, return_stats=True, return_status=True)
         return (mean if self.risk == "mean" else worst), functools.reduce(lambda u, v: u | v, status.unbind(-1))
 
 

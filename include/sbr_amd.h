@@ -341,6 +341,61 @@ int sbr_cycle_lookahead_scenarios(sbr_env* env, int32_t n_cycles, int32_t fanout
                                   int32_t* best_index, double* best_value,
                                   double* obs_end, double* diag_end, uint8_t* status_out, void* stream);
 
+/* ---- the per-cycle lookahead under UNCERTAIN PLANT KINETICS: futures over MODELS.  Every branch of the two calls above integrates
+ * the one plant the handle was created with.  The influent is half of what an operator does not know; the other half is the sludge:
+ * the ASM1 rate constants (muA above all), the yields, and the oxygen saturation, which moves with temperature.  A handle can hold
+ * a TABLE of plant models, and sbr_cycle_lookahead_models plays future s under model s % n_models of it - without a second
+ * handle per model.  sbr_reset / sbr_step / sbr_cycle_step and every other call keep integrating the handle's own config and return
+ * the same bits with or without a table.
+ *
+ * The MODEL FIELDS of sbr_config, the only ones in which a model may differ from the config of the handle:
+ *     Ya, Yh, fp, ixb, ixp, muH, Ks, Koh, Kno, bH, eta_g, eta_h, kh, Kx, muA, Knh, bA, Koa, ka, So_sat.
+ * Everything else - the time grid, the phase schedule, the controllers, the terminal phases, x0, the integrator, the dtypes, the
+ * reward kind - picks a kernel build, a loop count or a schedule the handle has already fixed, and must be equal byte for byte.
+ * A model is folded on the host exactly as sbr_create folds its config, so it carries its own stoichiometry, Monod denominators,
+ * scheme-1 step plan and SBR_ST_* pole thresholds.  cfg.scheme's VALIDITY DOMAIN (above) applies to every model on its own:
+ * kinetics several times faster than the reference's are outside what either scheme was validated on. */
+
+/* Host only, no device needed.  SBR_OK if `model` is a valid config (what sbr_create checks) that differs from `base` (NULL =
+ * the defaults) in model fields only.  Otherwise SBR_ERR_INVALID, and sbr_last_error(NULL) names this entry point and the first
+ * field of the struct outside the model fields that differs ("t_delta", "x0[3]", ...), or - the model fields alone differing -
+ * says what sbr_create would say about the config. */
+int sbr_check_model(const sbr_config* base /* NULL = defaults */, const sbr_config* model);
+
+/* The handle's model table: n_models configs, HOST pointer, each checked like sbr_check_model(the handle's config, model), folded
+ * and copied to a device table the handle owns.  Replaces an earlier table; n_models = 0 drops it; sbr_destroy frees it.  The
+ * allocation and the copy happen here and never at a launch, and the call waits for the device before an earlier table is freed
+ * (a launch that reads it may be in flight).  Nothing else of the handle changes.  SBR_ERR_INVALID, before anything is touched
+ * (the last failing check is reported): NULL env; n_models < 0; models NULL with n_models > 0; a model that fails the check
+ * (named by its index). */
+int sbr_set_models(sbr_env* env, int32_t n_models, const sbr_config* models /* HOST, [n_models] */);
+/* models in the handle's table, 0 if none is set.  NULL env: SBR_ERR_INVALID, reported through sbr_last_error(NULL). */
+int64_t sbr_num_models(const sbr_env* env);
+
+/* sbr_cycle_lookahead_scenarios with two differences.
+ *  (1) Future s runs under MODEL s % n_models of the handle's table, in every cycle: kinetics, stoichiometry, So_sat, the step plan
+ *      of cfg.scheme = 1, the thresholds behind status_out.  The handle's own constants are not read by any branch: a caller who wants
+ *      the nominal plant among the futures puts the handle's config into the table.  (n_scen and n_models are independent: n_scen =
+ *      n_models gives every model one future, n_scen = 3 n_models three influents per model.)
+ *  (2) influent may be NULL: every cycle of every future then runs under the env's STORED influent - sbr_cycle_lookahead's rule -
+ *      and the futures differ by their model alone.  Otherwise [n_cycles][N*n_scen][SBR_NX] as in the scenarios call.
+ * Everything else is that call's: a BRANCH is j = (i*fanout + k)*n_scen + s and B = N*fanout*n_scen < 2^31; the layouts of
+ * `actions` ([n_cycles][N*fanout][3], not expanded over s) and of every output; mean_out / worst_out / best_index / best_value
+ * and what they are reduced from; cycle c of branch j computing what sbr_cycle_reset(carry_over = 1, influent = its row) followed
+ * by sbr_cycle_step computes on a handle CREATED WITH THAT MODEL's config and holding the branch's state, with the same bits in
+ * every output.  NOTHING of the handle is written and nothing is allocated (graph-capturable).  The futures are the y axis of
+ * the launch grid, so that a model stays uniform across a wavefront; the register budget of the launch goes by B.
+ * n_cycles = 0 writes returns = mean_out = worst_out = 0, best_index = 0 and best_value = 0 and reads nothing.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): NULL env; no model table set; n_cycles < 0;
+ * n_scen < 1; n_scen > 65535; fanout < 1; N*fanout*n_scen >= 2^31; actions NULL with n_cycles > 0; obs_end, diag_end or status_out
+ * given with n_cycles = 0; mean_out or worst_out given while returns is NULL; best_index or best_value given while mean_out is
+ * NULL. */
+int sbr_cycle_lookahead_models(sbr_env* env, int32_t n_cycles, int32_t fanout, int32_t n_scen,
+                               const void* actions, const double* influent,
+                               double* returns, double* rewards_out, double* mean_out, double* worst_out,
+                               int32_t* best_index, double* best_value,
+                               double* obs_end, double* diag_end, uint8_t* status_out, void* stream);
+
 /* fused rollout with an on-device uniform random policy (BASELINE.json configs[4]): n_steps step()
  * calls per env in ONE kernel, plant state held in registers; actions ~ U[0,act_DO_max] x
  * U[0,act_EC_max] from Philox keyed by policy_seed, subsequence = global env id, counter = call index.
