@@ -80,6 +80,7 @@ SYMBOLS = {
     "sbr_set_influent_tables": (C.c_int, [_VP, _VP, _VP]),
     "sbr_reset": (C.c_int, [_VP, _U64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_reset_carry": (C.c_int, [_VP, _U64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_reset_models": (C.c_int, [_VP, _I64, _I32, _U64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_set_trace": (C.c_int, [_VP, _VP, _I64, _I64, _I32]),
     "sbr_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_cycle_reset": (C.c_int, [_VP, _U64, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
@@ -102,6 +103,7 @@ SYMBOLS = {
     "sbr_policy_param_count": (_I64, [_I32, _I32]),
     "sbr_rollout_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP]),
     "sbr_collect_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_collect_policy_models": (C.c_int, [_VP, _I64, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_lookahead_policy": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(SbrPolicy), _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                        _VP]),
     "sbr_reduce_stats": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),

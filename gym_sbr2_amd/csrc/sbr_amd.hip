@@ -7,6 +7,7 @@
 #include "sbr_policy.hip"
 #include "sbr_policy_lookahead.hip"
 #include "sbr_policy_collect.hip"
+#include "sbr_policy_collect_models.hip"
 #include "sbr_cycle_lookahead.hip"
 #include "sbr_cycle_scenarios.hip"
 #include "sbr_cycle_models.hip"

@@ -2,6 +2,7 @@
 // for the contract.  Kernels (all one-lane-per-env over SoA float64 state, 256-thread workgroups = four wavefronts, one per SIMD
 // of a CU, so a launch of N envs is N/64 independent waves that the dispatcher spreads over the 1024 SIMDs):
 //   k_reset    influent mix (tables in LDS) + fill phase (252 RK4 substeps under either scheme) + controller init + obs
+//   k_reset_models   k_reset with every env under its own plant model of the handle's table (sbr_reset_models)
 //   k_step     one SbrOS.step(): phase logic, 2 PIDs, the interval's integration (cfg.scheme 1: adaptive Butcher-5 steps per lane,
 //              sbr_b5a; scheme 0: 10 RK4 substeps; x2 at phase boundaries), reward,
 //              obs/state, and the terminal phases on the last call of an episode
@@ -13,7 +14,7 @@
 // What bounds them and how the arithmetic is organised for it: sbr_device.h (sbr_rates, sbr_rk4), DESIGN.md sections 3 and 5.
 // k_step is here and not in a unit of its own because its register allocation, and k_substeps', comes out differently when the
 // two are compiled apart (same instructions, other registers; profiles/r15_units_isa.txt): the layout follows the machine code.
-// Entry points: create / destroy / config / query, tables, the resets, trace, step, state get / set, influent and its futures, stats, the
+// Entry points: create / destroy / config / query, tables, the resets (sbr_reset_models among them), trace, step, state get / set, influent and its futures, stats, the
 // known-answer helpers, synchronize and the timers.  The calling thread's error text (sbr_last_error(NULL)) lives here.
 #include "sbr_host.h"
 
@@ -206,6 +207,84 @@ __global__ __launch_bounds__(BLK) void k_reset(SbrPar p, SbrBuf b, const double*
     store_x(b, i0, l, x);
     store_record<true>(p, b, i0, l, rec);
     if (obs) {   // volume blend of influent and post-fill state, :346-361
+        double xr[SBR_NX];
+        const double rwv = sbr_rcp(qin + iv);
+#pragma unroll
+        for (int j = 0; j < SBR_NX; ++j) xr[j] = (qin * ld[j] + x[j] * iv) * rwv;
+        double x06[SBR_NXD];
+        sbr_take6(x0, x06);
+        sbr_write_obs<OutT>(obs + i * SBR_NOBS, 1, c.t, xr, x06, x);
+    }
+}
+
+// k_reset over DOMAIN-RANDOMISED envs (sbr_reset_models): k_reset's body word for word - REPEATED and not shared, so that k_reset's
+// register allocation stays where it is - with `p` the model of the lane's WAVE in the handle's table (sbr_wave_model: model
+// (global id / envs_per_model) % n_models) and not the handle's own constants.  The fill phase, the status bits, the controller's
+// start values and the observation are then the model's; the influent draw reads nothing of the plant.  A 512-thread workgroup
+// may span two models: each wave reads its own.  The table's address is formed behind the bounds and mask tests, from the first
+// lane the wave still has; the lanes it still has all belong to one model.
+template <typename OutT, bool CARRY, int BLK = SBR_RESET_BLOCK>
+__global__ __launch_bounds__(BLK) void k_reset_models(const SbrPar* __restrict__ table, uint32_t n_models, int64_t envs_per_model, SbrBuf b,
+                                                      const double* __restrict__ tables, uint64_t seed,
+                                                      const int32_t* __restrict__ scenario, const double* __restrict__ rnd,
+                                                      const double* __restrict__ influent, const uint8_t* __restrict__ mask,
+                                                      OutT* __restrict__ obs) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];   // [2][8][SBR_TSTRIDE]
+    const bool need_tables = (influent == nullptr);
+    if (need_tables) {
+        stage_tables<BLK>(lds, tables);
+        __syncthreads();
+    }
+    const uint32_t l = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * BLK, i = i0 + l;
+    if (i >= b.n) return;
+    if (mask != nullptr && mask[i] == 0) return;
+    const uint64_t gid = (uint64_t)(b.first_env_id + i);
+    const SbrPar& p = *(const SbrPar*)sbr_wave_model(table, n_models, envs_per_model, gid);
+
+    double ld[SBR_NX];
+    influent_lane(lds, need_tables, pick_scenario(p, scenario, 6 /* :180 */, seed, gid, i), rnd, influent, seed, gid, i, ld);
+
+    double x[SBR_NX], x0[SBR_NX];
+    double iv = p.IV, qin = p.qin;
+    if (CARRY) {
+        load_x(b, i0, l, x0);
+        iv = x0[0]; qin = p.WV - iv;
+        ld[0] = qin * p.inv_T_fill;
+    } else {
+#pragma unroll
+        for (int j = 0; j < SBR_NX; ++j) {
+            x0[j] = p.x0[j];
+            asm volatile("" : "+v"(x0[j]));                          // held in VGPRs across the fill loop: see k_reset
+        }
+        ld[0] = p.load0;
+    }
+#pragma unroll
+    for (int j = 0; j < SBR_NX; ++j) { x[j] = x0[j]; INFL(j) = ld[j]; }
+
+    SbrRecord rec;
+    SbrCtl& c = rec.c;
+    const double e = 0.0 - x0[8];
+    double ie = 0.0;
+    double kla = p.Kc_DO * e + p.KcI_DO * ie;
+    if (kla > p.Kla_max) { kla = p.Kla_max; ie = ie - e * p.dt; }
+    if (kla < p.Kla_min) { kla = p.Kla_min; ie = ie - e * p.dt; }
+    sbr_rk4<2>(p, x, p.h_fill, p.fill_rows, kla, ld[0], ld);
+    c.t = p.T_fill;
+    c.so_m2 = x0[8]; c.so_m1 = x[8];
+    c.sno_m2 = x0[9]; c.sno_m1 = x[2];
+    c.ie_do = ie; c.ie_ec = 0.0; c.ec_last = 0.0; c.ec_prev = 0.0;
+    c.u_do = 0.0; c.u_ec = 15.0;
+#pragma unroll
+    for (int j = 0; j < SBR_KLA_HIST; ++j) rec.hist[j] = ((SBR_KLA_HIST - 1 - j) % 2 == 0) ? kla : 0.0;
+    c.kla_last = kla;
+    rec.ret = 0.0; rec.qw = 0.0;
+    rec.meta.status = sbr_status_bits(p, x);
+    rec.ksum = 0.0;
+    for (int j = 0; j < p.fill_rows / 2; ++j) rec.ksum = rec.ksum + kla;
+    store_x(b, i0, l, x);
+    store_record<true>(p, b, i0, l, rec);
+    if (obs) {
         double xr[SBR_NX];
         const double rwv = sbr_rcp(qin + iv);
 #pragma unroll
@@ -930,6 +1009,8 @@ void derive_params(const sbr_config& c, SbrPar& p) {
 template <typename T> using ResetFn = decltype(&k_reset<T, false>);
 template <typename T, int BLK> constexpr ResetFn<T> kReset[2] = {k_reset<T, false, BLK>, k_reset<T, true, BLK>};
 template <typename T> constexpr ResetFn<T> kCycleReset[2] = {k_cycle_reset<T, false>, k_cycle_reset<T, true>};
+template <typename T> using ResetModelsFn = decltype(&k_reset_models<T, false>);
+template <typename T, int BLK> constexpr ResetModelsFn<T> kResetModels[2] = {k_reset_models<T, false, BLK>, k_reset_models<T, true, BLK>};
 
 // What sbr_create has to say about a config; empty if it is valid.  Every check is evaluated and the LAST failing one is reported.
 std::string config_error(const sbr_config& c) {
@@ -1055,9 +1136,11 @@ int sbr_create(int64_t n_envs, int device_id, int64_t first_env_id, const sbr_co
     HIP_TRY(nullptr, hipEventCreate(&e->ev1));
     const int lds_bytes = kLdsTableDoubles * (int)sizeof(double);      // 84 KiB of dynamic LDS: above the 64 KiB default
     for (const int carry : {0, 1}) {
-        const void* fns[6] = {(const void*)kReset<float, SBR_RESET_BLOCK>[carry], (const void*)kReset<double, SBR_RESET_BLOCK>[carry],
-                              (const void*)kReset<float, 512>[carry], (const void*)kReset<double, 512>[carry],
-                              (const void*)kCycleReset<float>[carry], (const void*)kCycleReset<double>[carry]};
+        const void* fns[10] = {(const void*)kReset<float, SBR_RESET_BLOCK>[carry], (const void*)kReset<double, SBR_RESET_BLOCK>[carry],
+                               (const void*)kReset<float, 512>[carry], (const void*)kReset<double, 512>[carry],
+                               (const void*)kCycleReset<float>[carry], (const void*)kCycleReset<double>[carry],
+                               (const void*)kResetModels<float, SBR_RESET_BLOCK>[carry], (const void*)kResetModels<double, SBR_RESET_BLOCK>[carry],
+                               (const void*)kResetModels<float, 512>[carry], (const void*)kResetModels<double, 512>[carry]};
         for (const void* fn : fns) HIP_TRY(nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     }
     HIP_TRY(nullptr, hipFuncSetAttribute((const void*)k_draw_influent, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
@@ -1135,6 +1218,27 @@ int sbr_reset(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* 
 int sbr_reset_carry(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* rnd, const double* influent,
                     const uint8_t* mask, void* obs, void* stream) {
     return reset_impl(e, "sbr_reset", false, true, seed, scenario, rnd, influent, mask, obs, stream);
+}
+
+int sbr_reset_models(sbr_env* e, int64_t envs_per_model, int32_t carry_over, uint64_t seed, const int32_t* scenario, const double* rnd,
+                     const double* influent, const uint8_t* mask, void* obs, void* stream) {
+    std::string bad;                  // every check is evaluated, the LAST failing one is reported - before anything is touched
+    if (e && !influent && !e->have_tables) bad = "no influent given and sbr_set_influent_tables was never called";
+    const std::string mb = models_error(e, envs_per_model);
+    if (!mb.empty()) bad = mb;
+    if (!e) bad = "NULL env";
+    if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_reset_models: " + bad);
+    return launched(e, [&] {
+        const size_t lds = influent ? 0 : kLdsTableDoubles * sizeof(double);
+        const int blk = reset_block(e);
+        dispatch(e, [&](auto c) {
+            using T = typename decltype(c)::OutT;
+            const ResetModelsFn<T> fn = (blk == 512 ? kResetModels<T, 512> : kResetModels<T, SBR_RESET_BLOCK>)[carry_over != 0];
+            hipLaunchKernelGGL(fn, dim3((unsigned)((e->n + blk - 1) / blk)), dim3(blk), lds, (hipStream_t)stream,
+                               (const SbrPar*)e->models, (uint32_t)e->n_models, envs_per_model, e->buf, e->tables, seed, scenario, rnd,
+                               influent, mask, (T*)obs);
+        });
+    });
 }
 
 int sbr_cycle_reset(sbr_env* e, uint64_t seed, const int32_t* scenario, const double* rnd, const double* influent,

@@ -28,7 +28,6 @@
 // cycle, the constants through a pointer re-made per cycle at an offset of zero the compiler cannot see through (here the model's
 // address and not the kernel-argument segment's; the asm sits at the top of the loop, a wave-uniform path, so the offset is a
 // scalar), the sum and the status bits parked in LDS, no fetch ahead, the end rows stored inside the last cycle.
-typedef const __attribute__((address_space(4))) char* SbrConstBytes;
 template <typename ActT, int SCH>
 SBR_DEV void sbr_cycle_models_branch(const SbrPar* __restrict__ table, uint32_t n_models, SbrBuf b, int32_t n_cycles, uint32_t fanout,
                                      uint32_t n_scen, uint32_t n_pairs, const ActT* __restrict__ actions,
@@ -153,6 +152,21 @@ static std::string model_error(const sbr_config& base, const sbr_config& m) {
                       "So_sat, and nothing else";
     }
     return config_error(m);
+}
+
+// The rule of sbr_reset_models / sbr_collect_policy_models on this handle.  With more than one model a wave must never hold two:
+// the population rule of policy_error - blocks of a multiple of 256 envs, counted from a first env id that is one.
+std::string models_error(const sbr_env* e, int64_t envs_per_model) {
+    std::string bad;
+    if (!e) return bad;
+    if (e->n_models > 1) {
+        if (e->first_env_id < 0 || e->first_env_id % SBR_BLOCK != 0)
+            bad = "with more than one model the handle's first_env_id must be a non-negative multiple of 256";
+        if (envs_per_model < SBR_BLOCK || envs_per_model % SBR_BLOCK != 0)
+            bad = "with more than one model envs_per_model must be a positive multiple of 256";
+    }
+    if (e->n_models < 1) bad = "no model table: call sbr_set_models first";
+    return bad;
 }
 
 extern "C" {

@@ -125,9 +125,10 @@ static void launch_fused(const sbr_env* e, int64_t lanes, void* stream, Kernel&&
     hipLaunchKernelGGL(fn, grid_for(lanes), dim3(SBR_BLOCK), 0, (hipStream_t)stream, e->par, e->buf, args...);
 }
 
-// launch_fused on a two-dimensional grid, for the one kernel that reads its constants from the handle's model table and not from
-// e->par (k_cycle_lookahead_models, sbr_cycle_models.hip): lanes_x lanes along x, rows_y <= 65535 rows along y, the register
-// budget by their product.  e->models, e->n_models and e->buf lead the arguments.
+// launch_fused on a two-dimensional grid, for the kernels that read their constants from the handle's model table and not from
+// e->par (k_cycle_lookahead_models, sbr_cycle_models.hip; with rows_y = 1 k_models_collect_policy,
+// sbr_policy_collect_models.hip): lanes_x lanes along x, rows_y <= 65535 rows along y, the register budget by their product.
+// e->models, e->n_models and e->buf lead the arguments.
 template <int SCH, typename Kernel, typename... Args>
 static void launch_fused_models(const sbr_env* e, int64_t lanes_x, int32_t rows_y, void* stream, Kernel&& kernel, Args... args) {
     const auto fn = fused_waves_for(e, lanes_x * rows_y) == 1 ? kernel(std::integral_constant<int, kFusedOneWave<SCH>>{})
@@ -135,6 +136,11 @@ static void launch_fused_models(const sbr_env* e, int64_t lanes_x, int32_t rows_
     hipLaunchKernelGGL(fn, dim3(grid_for(lanes_x).x, (unsigned)rows_y), dim3(SBR_BLOCK), 0, (hipStream_t)stream,
                        (const SbrPar*)e->models, (uint32_t)e->n_models, e->buf, args...);
 }
+
+// What sbr_reset_models and sbr_collect_policy_models have to say about the rule "env g is plant (g / envs_per_model) % n_models"
+// on this handle (empty if it can be applied; the last failing check is reported; a NULL handle is the caller's to report):
+// defined in sbr_cycle_models.hip, next to the table.
+SBR_INTERNAL std::string models_error(const sbr_env* e, int64_t envs_per_model);
 
 // the type of a kernel's first parameter, for the units that assert the order launch_fused relies on
 template <typename F> struct SbrFirstParam;

@@ -192,6 +192,19 @@ SBR_DEV void store_record(const SbrPar& p, const SbrBuf& b, int64_t i0, uint32_t
     if (KSUM) CTRL(R_KSUM) = r.ksum;
 }
 
+// A plant model of the handle's table (sbr_set_models) as the kernels that integrate it hold it: a byte pointer in the constant
+// address space, so that every constant read through it is a scalar load (k_cycle_lookahead_models, k_models_collect_policy,
+// k_reset_models).
+typedef const __attribute__((address_space(4))) char* SbrConstBytes;
+// The model of the WAVE that holds the env with global id gid, under the rule of sbr_reset_models / sbr_collect_policy_models:
+// model (gid / envs_per_model) % n_models.  The host has checked that envs_per_model and the handle's first env id are multiples
+// of 256 where the table holds more than one model, so a wave never holds two; the readfirstlane makes the index - and with it
+// the address - a scalar.  With one model envs_per_model is not read.
+SBR_DEV SbrConstBytes sbr_wave_model(const SbrPar* __restrict__ table, uint32_t n_models, int64_t envs_per_model, uint64_t gid) {
+    uint32_t m = 0;
+    if (n_models > 1) m = __builtin_amdgcn_readfirstlane((uint32_t)((gid / (uint64_t)envs_per_model) % n_models));
+    return (SbrConstBytes)(table + m);
+}
 
 // A lane's pair of a row as one load (global_load_dwordx2 / dwordx4; the tape only has to be aligned like its elements).  The
 // compiler barrier behind it keeps the load where it is written: without it the compiler sank the fetch of the next row to the

@@ -100,17 +100,14 @@ class CycleLookahead:
         that differ from the env's config in the model fields only (models.MODEL_FIELDS); None or an empty sequence drops the
         table.  Replaces an earlier table, waiting for the device first.  reset(), step() and every other call keep
         integrating the env's own config."""
-        from .models import PlantModels
-        if models is not None and not isinstance(models, PlantModels):
-            models = PlantModels(models, base=self.cfg) if len(models) else None
-        n = 0 if models is None else len(models)
-        with torch.cuda.device(self.device):
-            _capi.check(self.lib.sbr_set_models(self._h, n, models.c_array() if n else None), self._h)
+        from .models import set_table
+        set_table(self, models)
 
     @property
     def num_models(self):
         """Models in the handle's table (sbr_num_models); 0 if none is set."""
-        return int(self.lib.sbr_num_models(self._h))
+        from .models import table_size
+        return table_size(self)
 
     def cycle_lookahead_models(self, candidates, influent=None, n_scen=None, return_rewards=False, return_stats=False,
                                return_best=False, return_end=False, return_status=False):
@@ -186,6 +183,9 @@ _REFUSED = {
     "lookahead_sampled_end": "the sampled lookahead",
     "lookahead_policy": "the closed-loop lookahead",
     "collect_policy": "the fused policy collector",
+    "reset_models": "the reset over domain-randomised envs",
+    "collect_policy_models": "the fused policy collector over domain-randomised envs",
+    "rollout_policy_models": "the fused policy rollout over domain-randomised envs",
     "branch_best": "the winner of a lookahead's branches",
     "mppi_update": "the MPPI tape update",
 }
@@ -197,5 +197,9 @@ def _refusal(phrase):
     return refuse
 
 
+# The refusals of the step-level models calls sit on the mixin, beside the set_models and num_models they would read: SBR-v2's
+# use of the table is cycle_lookahead_models.  (SbrEnv2Vec's own class body stays reset, step and the first nine.)
+_ON_MIXIN = ("reset_models", "collect_policy_models", "rollout_policy_models")
+
 for _name, _phrase in _REFUSED.items():
-    setattr(SbrEnv2Vec, _name, _refusal(_phrase))
+    setattr(CycleLookahead if _name in _ON_MIXIN else SbrEnv2Vec, _name, _refusal(_phrase))

@@ -20,6 +20,22 @@ def copy_config(cfg):
     return out
 
 
+def set_table(env, models):
+    """What set_models() of either vec env does: `models` (a PlantModels, a sequence of configs checked against env.cfg, or
+    None / empty to drop the table) becomes the table of env's handle (sbr_set_models)."""
+    import torch
+    if models is not None and not isinstance(models, PlantModels):
+        models = PlantModels(models, base=env.cfg) if len(models) else None
+    n = 0 if models is None else len(models)
+    with torch.cuda.device(env.device):
+        _capi.check(env.lib.sbr_set_models(env._h, n, models.c_array() if n else None), env._h)
+
+
+def table_size(env):
+    """What num_models of either vec env reports (sbr_num_models)."""
+    return int(env.lib.sbr_num_models(env._h))
+
+
 class PlantModels:
     """An ensemble of plant models: `configs` is a sequence of _capi.SbrConfig, each a valid config that differs from `base`
     (default: the first of them) in the MODEL_FIELDS only - sbr_check_model decides, and a config that fails raises ValueError with

@@ -148,6 +148,14 @@ _FORWARDED = {
     "rollout_policy": _WHOLE_POPULATION + "; `obs` [n_local, 18] is the rank's own slice.",
     "collect_policy": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every field of the result are the rank's own slices, and the "
                       "noise is keyed by the global env id.",
+    "set_models": "Every rank sets the WHOLE table: an env picks its model by its global id.",
+    "model_index": "The rule is keyed by the global env id, so a rank's entries are its slice of the single handle's.",
+    "reset_models": "Every input and `obs` are the rank's own slices; the plant of an env goes by its global id, so the result does "
+                    "not depend on the world size (with more than one model the rank's first global id must be a multiple of 256).",
+    "collect_policy_models": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every field of the result are the rank's own slices; "
+                             "plant and noise are keyed by the global env id.",
+    "rollout_policy_models": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every result are the rank's own slices; plant and noise "
+                             "are keyed by the global env id.",
     "lookahead_policy": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every result are the rank's own slices, and the noise of a "
                         "branch is keyed by its env's global id and its index among the env's branches.",
 }

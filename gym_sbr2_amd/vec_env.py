@@ -460,6 +460,10 @@ class SbrOSVec:
           returns  [N]           float64  the sum of this launch's rewards
           last_obs [N, 18]       float32  the in/out observation after the launch, for bootstrapping
         The action mean of a decision is the net applied to its row of `obs`; a learner recomputes it under autograd."""
+        return self._collect(self.lib.sbr_collect_policy, (), policy, n_steps, hold, obs, noise_std, noise_seed)
+
+    def _collect(self, fn, lead, policy, n_steps, hold, obs, noise_std, noise_seed):
+        """collect_policy and collect_policy_models: the outputs sized once, `lead` what the entry point takes behind the handle."""
         n_steps, hold = int(n_steps), int(hold)
         n, dev = self.num_envs, self.device
         o, pol = self._policy_inputs(policy, n_steps, hold, obs, noise_std, noise_seed)
@@ -471,10 +475,76 @@ class SbrOSVec:
         # (a tensor without elements reports a NULL pointer, and the library refuses the call without either per-decision output:
         # with n_steps = 0 the flags are the zero rows of a one-row buffer, which is not written)
         flags = torch.empty((max(rows, 1), n), dtype=torch.uint8, device=dev)
-        _capi.check(self.lib.sbr_collect_policy(self._h, n_steps, hold, C.byref(pol), _ptr(o), _ptr(ret), _ptr(acts), _ptr(rew),
-                                                _ptr(obs_out), _ptr(flags), self._stream()), self._h)
+        _capi.check(fn(self._h, *lead, n_steps, hold, C.byref(pol), _ptr(o), _ptr(ret), _ptr(acts), _ptr(rew), _ptr(obs_out),
+                       _ptr(flags), self._stream()), self._h)
         self._policy_obs_back(obs, o)
         return PolicyCollection(obs_out, acts, rew, flags[:rows], ret, o)
+
+    # ------------------------------------------------------------------ domain-randomised episodes: per-env plant models
+    def set_models(self, models):
+        """The handle's table of plant MODELS (sbr_set_models): `models` is a models.PlantModels or a sequence of _capi.SbrConfig
+        that differ from the env's config in the model fields only (models.MODEL_FIELDS); None or an empty sequence drops the
+        table.  Replaces an earlier table, waiting for the device first.  Only reset_models, collect_policy_models and
+        rollout_policy_models read it: reset(), step() and every other call keep integrating the env's own config."""
+        from .models import set_table
+        set_table(self, models)
+
+    @property
+    def num_models(self):
+        """Models in the handle's table (sbr_num_models); 0 if none is set."""
+        from .models import table_size
+        return table_size(self)
+
+    def model_index(self, envs_per_model):
+        """The plant of every env under THE RULE of reset_models / collect_policy_models, [N] int64, evaluated on the host: the env
+        with global id g = first_env_id + i is model (g // envs_per_model) % num_models.  With one model envs_per_model is not read.
+        ValueError where the library would refuse the rule: no table, or - with more than one model - envs_per_model or
+        first_env_id not a (positive) multiple of 256."""
+        m = int(self.num_models)
+        if m < 1:
+            raise ValueError("no model table: call set_models first")
+        if m == 1:
+            return torch.zeros((self.num_envs,), dtype=torch.int64)
+        per = int(envs_per_model)
+        if per < 256 or per % 256 or self.first_env_id < 0 or self.first_env_id % 256:
+            raise ValueError("with more than one model envs_per_model must be a positive multiple of 256 and first_env_id a "
+                             "non-negative multiple of 256")
+        return torch.div(self.first_env_id + torch.arange(self.num_envs, dtype=torch.int64), per, rounding_mode="floor") % m
+
+    def reset_models(self, envs_per_model, seed=0, scenario=None, rnd=None, influent=None, mask=None, carry_over=False):
+        """reset() over DOMAIN-RANDOMISED envs, one launch (sbr_reset_models): env i starts its episode as plant model_index(
+        envs_per_model)[i] of the table set_models() gave the handle - the fill phase, the status bits and the observation are
+        that model's, bit for bit what a handle created with the model's config returns.  Every argument but envs_per_model is
+        reset()'s."""
+        ins = self._reset_inputs(scenario, rnd, influent, mask)
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.sbr_reset_models(self._h, int(envs_per_model), 1 if carry_over else 0, C.c_uint64(int(seed)), *ins,
+                                                  _ptr(self.obs), self._stream()), self._h)
+        return self.obs
+
+    def collect_policy_models(self, policy, n_steps, envs_per_model, hold=1, obs=None, noise_std=None, noise_seed=0):
+        """collect_policy over DOMAIN-RANDOMISED envs, one launch (sbr_collect_policy_models): env i runs its calls as plant
+        model_index(envs_per_model)[i] of the handle's table - intervals, reward, status thresholds, step plan and terminal phases
+        are that model's - and every bit of the handle and of the PolicyCollection is what a handle created with the model's
+        config gives through collect_policy.  A population and the table vary independently.  Arguments otherwise, and the
+        result, are collect_policy's."""
+        return self._collect(self.lib.sbr_collect_policy_models, (int(envs_per_model),), policy, n_steps, hold, obs, noise_std,
+                             noise_seed)
+
+    def rollout_policy_models(self, policy, n_steps, envs_per_model, hold=1, obs=None, noise_std=None, noise_seed=0,
+                              return_actions=False, return_rewards=False):
+        """rollout_policy over DOMAIN-RANDOMISED envs (collect_policy_models' entry point without its two per-decision outputs):
+        rollout_policy's arguments plus envs_per_model, rollout_policy's results."""
+        n_steps, hold = int(n_steps), int(hold)
+        n = self.num_envs
+        o, pol = self._policy_inputs(policy, n_steps, hold, obs, noise_std, noise_seed)
+        ret = torch.empty((n,), dtype=torch.float64, device=self.device)
+        acts = torch.empty((-(-n_steps // hold), n, 2), dtype=torch.float32, device=self.device) if return_actions else None
+        rew = torch.empty((n_steps, n), dtype=torch.float64, device=self.device) if return_rewards else None
+        _capi.check(self.lib.sbr_collect_policy_models(self._h, int(envs_per_model), n_steps, hold, C.byref(pol), _ptr(o), _ptr(ret),
+                                                       _ptr(acts), _ptr(rew), None, None, self._stream()), self._h)
+        self._policy_obs_back(obs, o)
+        return _one_or_all((ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ()))
 
     def lookahead_policy(self, policy, fanout, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, keep_mean=False,
                          return_rewards=False, return_best=False, return_actions=False, return_end=False):

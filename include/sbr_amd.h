@@ -599,6 +599,41 @@ int sbr_rollout_policy(sbr_env* env, int32_t n_steps, int32_t hold, const sbr_po
 int sbr_collect_policy(sbr_env* env, int32_t n_steps, int32_t hold, const sbr_policy* policy, float* obs, double* returns,
                        float* actions_out, double* rewards_out, float* obs_out, uint8_t* flags_out, void* stream);
 
+/* ---- Domain-randomised episodes of SBROS-v1: the handle's own envs as DIFFERENT PLANTS -------------------------------------------
+ * A learner that has to survive a plant whose muA, bA or So_sat it does not know trains on many plants at once.  With a model
+ * table on the handle (sbr_set_models above) the two calls below run every env under a model of that table - one launch, one obs_out,
+ * one flags_out, global env ids and populations lined up as ever - where one handle per model would take a launch per model.
+ * THE RULE.  The env with global id g (the handle's first_env_id + its index) is plant (g / envs_per_model) % n_models.  It is keyed
+ * by the global id: it does not depend on N, on the shard or on the world size.  envs_per_model is an argument of each call and no
+ * state of the handle.  These two calls apply the rule and no others: sbr_reset, sbr_step, sbr_rollout*, sbr_collect_policy, every
+ * lookahead and the trace export keep integrating the handle's own config, with the bits they return without a table.
+ * CONDITIONS, checked before anything is touched (the last failing check is reported): a table is set (n_models >= 1); with
+ * n_models > 1, envs_per_model is a positive multiple of 256 and the handle's first_env_id a non-negative multiple of 256, so that a
+ * wavefront never holds two plants (a model's constants are wave-uniform scalar loads, as the handle's own are); with one model
+ * envs_per_model is not read.
+ * WHAT IS COMPUTED.  Every output bit - the plant, every controller row, the stored influent, and every buffer of the call - is what a
+ * second handle CREATED WITH THAT MODEL's config and the same first_env_id leaves for the same inputs through the parent call
+ * (sbr_reset / sbr_reset_carry; sbr_collect_policy or sbr_rollout_policy).  The table may be replaced between two launches
+ * (sbr_set_models waits for the device); nothing is allocated by either call (graph-capturable). */
+
+/* sbr_reset (carry_over = 0) / sbr_reset_carry (carry_over != 0) with the fill phase, the SBR_ST_* bits and the observation under
+ * each env's own model.  Everything else is the parent's: the influent draw keyed by seed and global id (it reads nothing of the
+ * plant), scenario, rnd, an explicit influent, mask, and obs in either output dtype.
+ * SBR_ERR_INVALID: NULL env; the conditions above; no influent given and sbr_set_influent_tables never called. */
+int sbr_reset_models(sbr_env* env, int64_t envs_per_model, int32_t carry_over, uint64_t seed, const int32_t* scenario,
+                     const double* rnd, const double* influent, const uint8_t* mask, void* obs, void* stream);
+
+/* sbr_collect_policy's loop with every constant read from the env's model: the control intervals, the reward, the SBR_ST_*
+ * thresholds, the step plan of cfg.scheme = 1 and the terminal phases.  Arguments, layouts and semantics are sbr_collect_policy's
+ * word for word, with one difference: obs_out and flags_out may BOTH be NULL - the call is then the models form of
+ * sbr_rollout_policy, and leaves its bits.  A population (policy->n_policies > 1) and a model table vary independently: the policy
+ * of an env is block g / envs_per_policy, its plant (g / envs_per_model) % n_models.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): every refusal of sbr_rollout_policy; the
+ * conditions above. */
+int sbr_collect_policy_models(sbr_env* env, int64_t envs_per_model, int32_t n_steps, int32_t hold, const sbr_policy* policy,
+                              float* obs, double* returns, float* actions_out, double* rewards_out, float* obs_out,
+                              uint8_t* flags_out, void* stream);
+
 /* CLOSED-LOOP lookahead: `fanout` rollouts of the caller's policy per env, each from the env's CURRENT state and observation, the
  * handle left bit for bit as it was (Monte-Carlo value and advantage estimates at the states the learner visits, policy-guided
  * MPC, n-step returns plus a critic on obs_end).  sbr_rollout_policy in the read-only, K-branches-per-env form of
