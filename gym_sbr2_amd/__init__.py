@@ -47,7 +47,8 @@ def __getattr__(name):          # torch is imported only when the env classes ar
     if name == "PlantModels":
         from .models import PlantModels
         return PlantModels
-    if name in ("TapeSampler", "MppiPlanner", "PolicyRolloutPlanner", "CycleSetpointSearch", "RobustCycleSetpointSearch"):
+    if name in ("TapeSampler", "MppiPlanner", "RobustMppiPlanner", "PolicyRolloutPlanner", "CycleSetpointSearch",
+                "RobustCycleSetpointSearch"):
         from . import planner
         return getattr(planner, name)
     raise AttributeError(name)

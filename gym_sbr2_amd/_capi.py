@@ -104,6 +104,9 @@ SYMBOLS = {
     "sbr_rollout_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP]),
     "sbr_collect_policy": (C.c_int, [_VP, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "sbr_collect_policy_models": (C.c_int, [_VP, _I64, _I32, _I32, C.POINTER(SbrPolicy), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_lookahead_actions_models": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "sbr_lookahead_sampled_models": (C.c_int, [_VP, _I32, _I32, _I32, _VP, C.POINTER(SbrSampler), _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                               _VP]),
     "sbr_lookahead_policy": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(SbrPolicy), _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                        _VP]),
     "sbr_reduce_stats": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),

@@ -23,7 +23,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SOURCES = [os.path.join(_CSRC, n) for n in ("sbr_core.hip", "sbr_rollout.hip", "sbr_tape.hip", "sbr_sampled.hip", "sbr_policy.hip",
                                             "sbr_policy_lookahead.hip", "sbr_policy_collect.hip", "sbr_policy_collect_models.hip",
-                                            "sbr_cycle_lookahead.hip", "sbr_cycle_scenarios.hip", "sbr_cycle_models.hip")]
+                                            "sbr_cycle_lookahead.hip", "sbr_cycle_scenarios.hip", "sbr_cycle_models.hip",
+                                            "sbr_lookahead_models.hip")]
 SRC = os.path.join(_CSRC, "sbr_amd.hip")      # the units of SOURCES as one translation unit (#include lines only), for one-file tools
 DEPS = SOURCES + [os.path.join(_CSRC, n) for n in ("sbr_kernels.h", "sbr_host.h", "sbr_policy.h", "sbr_device.h")] + [
     os.path.join(os.path.dirname(_HERE), "include", "sbr_amd.h")]

@@ -11,3 +11,4 @@
 #include "sbr_cycle_lookahead.hip"
 #include "sbr_cycle_scenarios.hip"
 #include "sbr_cycle_models.hip"
+#include "sbr_lookahead_models.hip"

@@ -153,6 +153,13 @@ SBR_INTERNAL void best_error(std::string& bad, const double* returns, const int3
 SBR_INTERNAL std::string end_error(int32_t n_steps, const void* obs_end, const void* state_end, const void* done_end);
 SBR_INTERNAL void launch_branch_best(const sbr_env* e, int32_t fanout, const double* values, int32_t* best_index, double* best_value,
                                      void* stream);
+// What sbr_lookahead_actions / sbr_lookahead_sampled (and their _end forms) have to say about the arguments they share, for the
+// models forms of the two (sbr_lookahead_models.hip): defined in sbr_tape.hip and in sbr_sampled.hip, next to the entry points.
+SBR_INTERNAL std::string lookahead_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions,
+                                         const double* returns, const int32_t* best_index, const double* best_return);
+SBR_INTERNAL std::string lookahead_sampled_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
+                                                 const sbr_sampler* sampler, const double* returns, const int32_t* best_index,
+                                                 const double* best_return);
 // k_scenario_stats for a caller outside its unit (sbr_cycle_scenarios.hip owns it): mean and worst of each pair's n_scen returns
 SBR_INTERNAL void launch_scenario_stats(const double* returns, int64_t n_pairs, int32_t n_scen, double* mean_out, double* worst_out,
                                         void* stream);

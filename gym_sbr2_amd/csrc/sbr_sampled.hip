@@ -226,9 +226,9 @@ static std::string sampler_error(const sbr_env* e, const sbr_sampler* sm, int32_
     return bad;
 }
 // The same for sbr_lookahead_sampled and sbr_lookahead_sampled_end: the LAST failing check is reported.
-static std::string lookahead_sampled_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
-                                           const sbr_sampler* sampler, const double* returns, const int32_t* best_index,
-                                           const double* best_return) {
+std::string lookahead_sampled_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
+                                    const sbr_sampler* sampler, const double* returns, const int32_t* best_index,
+                                    const double* best_return) {
     std::string bad;
     best_error(bad, returns, best_index, best_return);
     if (!nominal && n_steps > 0) bad = "NULL nominal with n_steps > 0";

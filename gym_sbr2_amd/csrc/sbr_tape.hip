@@ -204,8 +204,8 @@ void best_error(std::string& bad, const double* returns, const int32_t* best_ind
 }
 // What sbr_lookahead_actions and sbr_lookahead_actions_end have to say about the arguments they share; empty if they are valid.
 // Every check is evaluated, the LAST failing one is reported - all of them before anything is touched.
-static std::string lookahead_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions,
-                                   const double* returns, const int32_t* best_index, const double* best_return) {
+std::string lookahead_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions, const double* returns,
+                            const int32_t* best_index, const double* best_return) {
     std::string bad;
     best_error(bad, returns, best_index, best_return);
     if (!actions && n_steps > 0) bad = "NULL actions with n_steps > 0";

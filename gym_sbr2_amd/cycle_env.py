@@ -186,6 +186,8 @@ _REFUSED = {
     "reset_models": "the reset over domain-randomised envs",
     "collect_policy_models": "the fused policy collector over domain-randomised envs",
     "rollout_policy_models": "the fused policy rollout over domain-randomised envs",
+    "lookahead_models": "the read-only lookahead over plant models",
+    "lookahead_sampled_models": "the sampled lookahead over plant models",
     "branch_best": "the winner of a lookahead's branches",
     "mppi_update": "the MPPI tape update",
 }
@@ -199,7 +201,7 @@ def _refusal(phrase):
 
 # The refusals of the step-level models calls sit on the mixin, beside the set_models and num_models they would read: SBR-v2's
 # use of the table is cycle_lookahead_models.  (SbrEnv2Vec's own class body stays reset, step and the first nine.)
-_ON_MIXIN = ("reset_models", "collect_policy_models", "rollout_policy_models")
+_ON_MIXIN = ("reset_models", "collect_policy_models", "rollout_policy_models", "lookahead_models", "lookahead_sampled_models")
 
 for _name, _phrase in _REFUSED.items():
     setattr(CycleLookahead if _name in _ON_MIXIN else SbrEnv2Vec, _name, _refusal(_phrase))

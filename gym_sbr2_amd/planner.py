@@ -82,18 +82,58 @@ class MppiPlanner:
         return_returns=True also the candidates' returns [N, K]."""
         sm = self.sampler.with_seed(self.sampler.seed + self.decision)
         if self.terminal_value is None:
-            ret = self.env.lookahead_sampled(self.nominal, self.fanout, sm, hold=self.hold)
+            scored = self._score(sm)
         else:
             ret, obs_end, state_end, done_end = self.env.lookahead_sampled_end(self.nominal, self.fanout, sm, hold=self.hold)
             v = self.terminal_value(obs_end, state_end).double()
-            ret = (ret + v.masked_fill(done_end, 0.0)).contiguous()
+            scored = ((ret + v.masked_fill(done_end, 0.0)).contiguous(),)
         self._cur ^= 1
         buf = self._bufs[self._cur]
-        self.env.mppi_update(self.nominal, ret, sm, self.temperature, out=buf[:self.rows])
+        self.env.mppi_update(self.nominal, scored[0], sm, self.temperature, out=buf[:self.rows])
         buf[self.rows].copy_(buf[self.rows - 1])
         self.nominal = buf[1:]
         self.decision += 1
-        return (buf[0], ret) if return_returns else buf[0]
+        return (buf[0],) + scored if return_returns else buf[0]
+
+    def _score(self, sm):
+        """What the candidates drawn by `sm` around the nominal tape are worth without a terminal value: a tuple whose first member
+        [N, K] float64 is what mppi_update weighs them by; plan(return_returns=True) returns all of it behind the action."""
+        return (self.env.lookahead_sampled(self.nominal, self.fanout, sm, hold=self.hold),)
+
+
+class RobustMppiPlanner(MppiPlanner):
+    """MppiPlanner when the plant's kinetics are NOT known: the same loop - the two buffers, the seed per decision, mppi_update -
+    with every candidate tape scored under every model of the table `env` holds (env.set_models(...); lookahead_sampled_models,
+    one launch, the handle untouched).  All models of a candidate play the same tape, so two candidates differ by what they do and
+    not by what they drew.  risk="mean" weighs a candidate by the mean of its M returns, risk="worst" by the smallest of them.
+    The env's own config is scored only if it stands in the table.
+
+        env.set_models(PlantModels.perturbed(env.cfg, 8, rel_std=0.1))
+        planner = RobustMppiPlanner(env, rows=50, fanout=64, sampler=TapeSampler((0.3, 2.0)), temperature=5.0, risk="worst")
+        while ...: env.step(planner.plan())
+
+    plan(return_returns=True) returns (action, the statistic the candidates were weighed by [N, K], every branch's return
+    [N, K, M]).  There is no terminal value: the lookahead over models has no _end form, and assigning one raises ValueError.
+    """
+
+    def __init__(self, env, rows, fanout, sampler, temperature, hold=1, risk="mean"):
+        if risk not in ("mean", "worst"):
+            raise ValueError('risk must be "mean" or "worst"')
+        super().__init__(env, rows, fanout, sampler, temperature, hold)
+        self.risk = risk
+
+    @property
+    def terminal_value(self):
+        return None
+
+    @terminal_value.setter
+    def terminal_value(self, value):
+        if value is not None:
+            raise ValueError("RobustMppiPlanner takes no terminal_value: the lookahead over models has no _end form")
+
+    def _score(self, sm):
+        ret, mean, worst = self.env.lookahead_sampled_models(self.nominal, self.fanout, sm, hold=self.hold, return_stats=True)
+        return (mean if self.risk == "mean" else worst), ret
 
 
 class CycleSetpointSearch:

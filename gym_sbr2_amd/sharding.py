@@ -156,6 +156,10 @@ _FORWARDED = {
                              "plant and noise are keyed by the global env id.",
     "rollout_policy_models": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every result are the rank's own slices; plant and noise "
                              "are keyed by the global env id.",
+    "lookahead_models": "`actions` [R, n_local, K, 2] is the rank's own slice of the candidates and every result the rank's own slice; "
+                        "every rank holds the WHOLE table, and every env meets every model of it.",
+    "lookahead_sampled_models": "`nominal` [R, n_local, 2] is the rank's own slice of the nominal tape; the candidates are keyed by the "
+                                "global env id (and not by the model), so the results do not depend on the world size.",
     "lookahead_policy": _WHOLE_POPULATION + "; `obs` [n_local, 18] and every result are the rank's own slices, and the noise of a "
                         "branch is keyed by its env's global id and its index among the env's branches.",
 }

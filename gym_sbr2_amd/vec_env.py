@@ -484,8 +484,9 @@ class SbrOSVec:
     def set_models(self, models):
         """The handle's table of plant MODELS (sbr_set_models): `models` is a models.PlantModels or a sequence of _capi.SbrConfig
         that differ from the env's config in the model fields only (models.MODEL_FIELDS); None or an empty sequence drops the
-        table.  Replaces an earlier table, waiting for the device first.  Only reset_models, collect_policy_models and
-        rollout_policy_models read it: reset(), step() and every other call keep integrating the env's own config."""
+        table.  Replaces an earlier table, waiting for the device first.  Only reset_models, collect_policy_models,
+        rollout_policy_models (a plant per env) and lookahead_models, lookahead_sampled_models (every env under every model) read
+        it: reset(), step() and every other call keep integrating the env's own config."""
         from .models import set_table
         set_table(self, models)
 
@@ -545,6 +546,54 @@ class SbrOSVec:
                                                        _ptr(acts), _ptr(rew), None, None, self._stream()), self._h)
         self._policy_obs_back(obs, o)
         return _one_or_all((ret,) + ((acts,) if return_actions else ()) + ((rew,) if return_rewards else ()))
+
+    # ------------------------------------------------------------------ lookahead under uncertain plant kinetics: K tapes x M models
+    def _models_branches(self, fanout):
+        """M of a lookahead over (env, candidate, model) branches, checked before any output is sized by it."""
+        m = int(self.num_models)
+        if m < 1:
+            raise ValueError("no model table: call set_models first")
+        if fanout >= 1 and self.num_envs * fanout * m >= 2 ** 31:
+            raise ValueError("num_envs * K * num_models must stay below 2^31")
+        return m
+
+    def lookahead_models(self, actions, n_steps=None, hold=1, return_rewards=False, return_stats=False, return_best=False):
+        """lookahead under UNCERTAIN PLANT KINETICS, one launch (sbr_lookahead_actions_models): `actions` is [R, N, K, 2] as for
+        lookahead, and every candidate of every env is played from the env's CURRENT state under EVERY model of the table
+        set_models() gave the handle - branch (i, k, m) under the constants of model m.  The env's own config is integrated by no
+        branch (put it into the table to have the nominal plant among the models); the handle is left bit for bit as it was.
+        Returns the sum of this launch's rewards per branch [N, K, M] float64 - column m is, bit for bit, what lookahead returns
+        on a handle created with model m's config that holds the env's state - then, in this order and only if asked for: the
+        reward of every call [n_steps, N, K, M] (a strided store on the device: ask for it when it is needed); mean and worst
+        [N, K], the mean over m (summed in m order, one division) and the smallest of a candidate's M returns, NaN if one of them
+        is; best_index [N] int32 and best_value [N] float64, the winner among an env's means (lookahead's rule).  No _end form."""
+        hold = int(hold)
+        a, rows, n_steps = self._tape(actions, (self.num_envs, None, 2), n_steps, hold)
+        fanout = int(a.shape[2])
+        m = self._models_branches(fanout)
+        ptrs, _, results = self._fanout_outputs(fanout, n_steps, hold, return_rewards, return_best, False, n_scen=m,
+                                                return_stats=return_stats)
+        _capi.check(self.lib.sbr_lookahead_actions_models(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, *ptrs,
+                                                          self._stream()), self._h)
+        return results
+
+    def lookahead_sampled_models(self, nominal, fanout, sampler, n_steps=None, hold=1, return_rewards=False, return_stats=False,
+                                 return_best=False, return_actions=False):
+        """lookahead_models over SAMPLED tapes (sbr_lookahead_sampled_models): `nominal` [R, N, 2] and `sampler` as for
+        lookahead_sampled.  Candidate k of an env is keyed by (seed, global env id, k, row) and NOT by the model: all M models of
+        a candidate play the same tape (common random numbers), so two models differ by the plant and not by what they drew.
+        Results and their order are lookahead_models' - returns [N, K, M], column m the bits of lookahead_sampled on a handle
+        created with model m's config; rewards; mean, worst; best_index, best_value - then with return_actions=True the
+        candidates exactly as they were integrated [R, N, K, 2] (fed to lookahead_models they give the same bits)."""
+        hold, fanout = int(hold), int(fanout)
+        a, rows, n_steps = self._tape(nominal, self._ashape, n_steps, hold)
+        m = self._models_branches(fanout)
+        sm = sampler.c_struct(self.cfg)
+        ptrs, _, results = self._fanout_outputs(fanout, n_steps, hold, return_rewards, return_best, False, return_actions,
+                                                self.action_dtype, n_scen=m, return_stats=return_stats)
+        _capi.check(self.lib.sbr_lookahead_sampled_models(self._h, n_steps, hold, fanout, _ptr(a) if rows else None, C.byref(sm),
+                                                          *ptrs, self._stream()), self._h)
+        return results
 
     def lookahead_policy(self, policy, fanout, n_steps, hold=1, obs=None, noise_std=None, noise_seed=0, keep_mean=False,
                          return_rewards=False, return_best=False, return_actions=False, return_end=False):

@@ -606,7 +606,8 @@ int sbr_collect_policy(sbr_env* env, int32_t n_steps, int32_t hold, const sbr_po
  * THE RULE.  The env with global id g (the handle's first_env_id + its index) is plant (g / envs_per_model) % n_models.  It is keyed
  * by the global id: it does not depend on N, on the shard or on the world size.  envs_per_model is an argument of each call and no
  * state of the handle.  These two calls apply the rule and no others: sbr_reset, sbr_step, sbr_rollout*, sbr_collect_policy, every
- * lookahead and the trace export keep integrating the handle's own config, with the bits they return without a table.
+ * lookahead but the two *_models forms further down (which play every env under every model) and the trace export keep integrating
+ * the handle's own config, with the bits they return without a table.
  * CONDITIONS, checked before anything is touched (the last failing check is reported): a table is set (n_models >= 1); with
  * n_models > 1, envs_per_model is a positive multiple of 256 and the handle's first_env_id a non-negative multiple of 256, so that a
  * wavefront never holds two plants (a model's constants are wave-uniform scalar loads, as the handle's own are); with one model
@@ -633,6 +634,53 @@ int sbr_reset_models(sbr_env* env, int64_t envs_per_model, int32_t carry_over, u
 int sbr_collect_policy_models(sbr_env* env, int64_t envs_per_model, int32_t n_steps, int32_t hold, const sbr_policy* policy,
                               float* obs, double* returns, float* actions_out, double* rewards_out, float* obs_out,
                               uint8_t* flags_out, void* stream);
+
+/* ---- the step-level lookahead under UNCERTAIN PLANT KINETICS: K tapes x M models -------------------------------------------------
+ * sbr_lookahead_actions / sbr_lookahead_sampled integrate the handle's own plant.  The two calls below play every candidate tape of
+ * every env under EVERY model of the handle's table (sbr_set_models above; M = sbr_num_models(env)) in one launch, and reduce
+ * mean / worst / winner on the device: "which tape is good if muA, bA or So_sat is not what I think?" without a handle, a copy of
+ * the live state and a launch per model.  (The rule of the two calls above - a plant per env - is NOT applied here: every env
+ * meets every model.)
+ * A BRANCH is (env i, candidate k, model m), j = (i*fanout + k)*M + m; there are B = N*fanout*M < 2^31 of them.  Branch (i, k, m)
+ * plays candidate k of env i from env i's CURRENT plant and controller record under the constants of model m: intervals, reward,
+ * SBR_ST_* thresholds, the step plan of cfg.scheme = 1.  The handle's own config is integrated by NO branch: a caller who wants
+ * the nominal plant among the models puts the handle's config into the table.
+ *   actions     [ceil(n_steps / hold)][N*fanout][2] ActT, nominal [ceil(n_steps / hold)][N][2] ActT: exactly the parents' inputs,
+ *               not expanded over m
+ *   returns     [B] float64 or NULL: the per-branch sum of the launch's rewards, added in call order
+ *   rewards_out [n_steps][B] float64 or NULL: the reward of every call, 0.0 for a call a finished branch skipped.  A STRIDED
+ *               store: the lanes of a wavefront hold neighbouring (i, k) of one m, so each call writes 64 doubles M apart - ask
+ *               for it when the per-call rewards are needed, not by default
+ *   mean_out, worst_out [N*fanout] float64 or NULL: over a candidate's M returns - the rule of sbr_cycle_lookahead_scenarios:
+ *               summed in m order and divided once; the smallest return; NaN if one of them is.  Reduced FROM `returns`, which
+ *               must be given with them
+ *   best_index  [N] int32 or NULL, best_value [N] float64 or NULL: the winner among an env's `fanout` MEANS under
+ *               sbr_lookahead_actions' rule; reduced FROM mean_out, which must be given with them
+ *   actions_out [ceil(n_steps / hold)][N*fanout][2] ActT or NULL (sampled call): the candidates as integrated.  A candidate is
+ *               a(g, k, r, c) - keyed by (seed, global env id, k, row) and NOT by m: all models of a candidate play the SAME
+ *               tape (common random numbers), so that two models differ by the plant and not by what they drew.  Stored once,
+ *               by the branches of model 0
+ * THE CONTRACT.  returns[i][k][m] and rewards_out[.][i][k][m] carry the bits sbr_lookahead_actions gives for candidate k of env
+ * i on a second handle CREATED WITH MODEL m's config and the same first_env_id that holds env i's state (sbr_get_state /
+ * sbr_set_state); the sampled call likewise the bits of sbr_lookahead_sampled on such a handle.  With the handle's own config at
+ * table index m, column m holds the bits of the parent call on the handle itself.  Fed its own actions_out,
+ * sbr_lookahead_actions_models returns the bits of sbr_lookahead_sampled_models.
+ * In every other respect the calls are their parents: rows held `hold` calls and launch-relative, a done branch skips its
+ * remaining calls, no terminal phases, the end-of-cycle reward of reward_kind 2 inside the done call.  NOTHING of the handle is
+ * written, nothing is allocated (graph-capturable).  The models are the y axis of the launch grid, so that a model stays uniform
+ * across a wavefront and is read with scalar loads; the register budget of the launch goes by B.
+ * n_steps = 0 writes returns = mean_out = worst_out = 0, best_index = 0 and best_value = 0 and reads nothing of the state, the
+ * tape or the table.
+ * NOT HERE: _end forms (where each branch ended), a policy lookahead over models, sbr_step under a model.
+ * SBR_ERR_INVALID, before anything is touched (the last failing check is reported): every refusal of the parent but the one
+ * about best_* (here: best_index or best_value given while mean_out is NULL); no model table set; more than 65535 models;
+ * N*fanout*M >= 2^31; mean_out or worst_out given while returns is NULL. */
+int sbr_lookahead_actions_models(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const void* actions,
+                                 double* returns, double* rewards_out, double* mean_out, double* worst_out,
+                                 int32_t* best_index, double* best_value, void* stream);
+int sbr_lookahead_sampled_models(sbr_env* env, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
+                                 const sbr_sampler* sampler, double* returns, double* rewards_out, double* mean_out,
+                                 double* worst_out, int32_t* best_index, double* best_value, void* actions_out, void* stream);
 
 /* CLOSED-LOOP lookahead: `fanout` rollouts of the caller's policy per env, each from the env's CURRENT state and observation, the
  * handle left bit for bit as it was (Monte-Carlo value and advantage estimates at the states the learner visits, policy-guided
