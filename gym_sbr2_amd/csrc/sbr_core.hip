@@ -368,7 +368,8 @@ SBR_DEV void store_rows(OutT* __restrict__ rows /* out + i0*NV: first row of the
 // read every 16-byte chunk into registers, then issue the stores.  The stores are inline assembly with a memory clobber (the
 // sc1 modifier has no builtin for 16 bytes), which the compiler will not move an LDS read across: read-store-read-store cost
 // one exposed LDS round trip per chunk (nine per call until round 4).  `stage` must hold 64 (RB_A + RB_B) bytes.
-template <typename OutT, int NA, int NB>
+// COLD_DIRECT: the direct form (ragged wave, misaligned destination) is marked unlikely and laid out behind the caller's hot code.
+template <typename OutT, int NA, int NB, bool COLD_DIRECT = false>
 SBR_DEV void store_rows2(OutT* __restrict__ rows_a, OutT* __restrict__ rows_b, uint32_t l, char* stage, bool wide,
                          const OutT (&va)[NA], const OutT (&vb)[NB]) {
     constexpr int RA = NA * (int)sizeof(OutT), RBB = NB * (int)sizeof(OutT);
@@ -377,7 +378,7 @@ SBR_DEV void store_rows2(OutT* __restrict__ rows_a, OutT* __restrict__ rows_b, u
     const uint32_t lane = l & 63u;
     char* wa = reinterpret_cast<char*>(rows_a + (size_t)(l & ~63u) * NA);
     char* wb = reinterpret_cast<char*>(rows_b + (size_t)(l & ~63u) * NB);
-    if (wide && ((reinterpret_cast<uintptr_t>(wa) | reinterpret_cast<uintptr_t>(wb)) & 15u) == 0) {
+    if (SBR_USUAL_IF(COLD_DIRECT, wide && ((reinterpret_cast<uintptr_t>(wa) | reinterpret_cast<uintptr_t>(wb)) & 15u) == 0)) {
         // The staging region is the wave's parking space, whose slots were read as float64 just before: to the compiler's
         // type-based alias analysis a float32 store and a float64 load never alias, so without this barrier it may hoist the
         // staging stores above those loads (seen in round 4: rows 27.. of the float32 outputs held parked values).
@@ -595,7 +596,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         // or a rollout fetches the rows (a second, dependent load: once per episode)
         c.so_m1 = x[8]; c.sno_m1 = x[9];
         const bool m1_rows = ((int)meta0 & SbrMeta::kM1i) == 0;
-        if (__builtin_amdgcn_ballot_w64(m1_rows) != 0ull) {
+        if (SBR_RARE_IF(AGAIN, __builtin_amdgcn_ballot_w64(m1_rows) != 0ull)) {
             if (m1_rows) { c.so_m1 = CTRL(R_SO_M1); c.sno_m1 = CTRL(R_SNO_M1); }
         }
         if ((flags & SBR_KF_NEED_M2) == 0u) { c.so_m2 = c.so_m1; c.sno_m2 = c.sno_m1; }
@@ -622,7 +623,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         SbrHistInc hs{my[SBR_PK_W8 * 64], kla_before_r, {lv[0], lv[1], lv[2]}, 0.0, false};
         if constexpr (!PARK) x6.get(xa6);
         double ksum = OCI ? my[SBR_PK_KSUM * 64] : 0.0;
-        r = sbr_finish_step<OCI, SCH, SbrHistInc, true, SbrX6LdsT<PARK>>(pe, c, hs, x, xa6, t_obs, dn, qw, ksum, rp, &x6);
+        r = sbr_finish_step<OCI, SCH, SbrHistInc, true, SbrX6LdsT<PARK>, AGAIN>(pe, c, hs, x, xa6, t_obs, dn, qw, ksum, rp, &x6);
         if constexpr (PARK) x6.get(xa6);              // after the terminal phases, which leave their pre-settle values in the slots
         SBR_STAMP(4, false);                  // reward (and, on the done call, the terminal phases) done
         // everything that reads the three ring entries loaded before the integration comes BEFORE the first store: the memory
@@ -645,7 +646,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         SBR_STAMP(9, false);                  // plant stores issued
         // So[-1], Sno[-1] stay implicit unless this was the done call (the terminal phases have moved x away from them)
         store_ctl(b, i0, l, c, false);
-        if (__builtin_amdgcn_ballot_w64(dn) != 0ull) {
+        if (SBR_RARE_IF(AGAIN, __builtin_amdgcn_ballot_w64(dn) != 0ull)) {
             if (dn) { CTRL(R_SO_M1) = c.so_m1; CTRL(R_SNO_M1) = c.sno_m1; }
         }
         // the Kla ring is addressed by the interval count: envs reset together share it, so the slot is normally
@@ -656,18 +657,18 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         const bool idle_pushed = hs.idle_pushed;
         const double app0 = c.n_new > 0 ? c.knew[0] : hs.idle;            // the appended values in order: knew[0], knew[1], idle
         const int n_app = c.n_new + (idle_pushed ? 1 : 0);
-        if (ring_uniform) {
+        if (SBR_USUAL_IF(AGAIN, ring_uniform)) {
             if (n_app > 0) st_out(&CTRL(R_RING0 + kb_u), app0);
         } else {
             if (n_app > 0) CTRL(R_RING0 + kb) = app0;
         }
-        if (__builtin_amdgcn_ballot_w64(n_app > 1) != 0ull) {
+        if (SBR_RARE_IF(AGAIN, __builtin_amdgcn_ballot_w64(n_app > 1) != 0ull)) {
             const double app1 = c.n_new > 1 ? c.knew[1] : hs.idle;
             if (n_app > 1) CTRL(R_RING0 + ring_wrap(kb + 1)) = app1;
             if (n_app > 2) CTRL(R_RING0 + ring_wrap(kb + 2)) = hs.idle;
         }
         st_out(&CTRL(R_KLA_LAST), last_new); st_out(&CTRL(R_W8), w8_new);
-        if (dn && pe.terminal) CTRL(R_QW) = qw;
+        if (SBR_RARE_IF(AGAIN, dn && pe.terminal)) CTRL(R_QW) = qw;
         const SbrMeta m = SbrMeta::unpack(my[SBR_PK_META * 64]);
         const int steps = m.steps;
         st_out(&CTRL(R_RET), my[SBR_PK_RET * 64] + r);
@@ -676,7 +677,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         const bool m1i_new = dn ? false : (c.n_new > 0 ? true : !m1_rows);
         st_out(&CTRL(R_META), SbrMeta::pack({SbrMeta::next_steps(steps), m.status | c.st_new, dn, idle_pushed, m1i_new, c.plans & 0xff}));
         SBR_STAMP(10, false);                 // controller stores issued
-        if (b.trace != nullptr && i0 + l < b.n_trace && (int64_t)steps < b.trace_cap) {     // trajectory export, off by default
+        if (SBR_RARE_IF(AGAIN, b.trace != nullptr && i0 + l < b.n_trace && (int64_t)steps < b.trace_cap)) {     // trajectory export, off by default
             double* rec = b.trace + ((int64_t)steps * SBR_NTRACE) * b.n_trace + (i0 + l);
             rec[0] = c.t;
 #pragma unroll
@@ -706,7 +707,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
     char* stage = reinterpret_cast<char*>(wave_lds);
     // both row sets fit the wave's staging region together when they are float32 (64 x (72 + 60) = 8448 of the region's 10240 bytes: 20 slots x 512)
     constexpr bool kBoth = 64 * (SBR_NOBS + SBR_NSTATE) * (int)sizeof(OutT) <= NSLOT * 64 * (int)sizeof(double);
-    if (kBoth && obs && state) {
+    if (SBR_USUAL_IF(AGAIN, kBoth && obs && state)) {
         OutT o[SBR_NOBS], sv[SBR_NSTATE];
         sbr_write_obs<OutT>(o, 1, t_obs, x, xa6, x);
         sbr_write_state<OutT>(sv, 1, t_obs, x);
@@ -714,7 +715,7 @@ __global__ __launch_bounds__(BLK, BLK == 256 && WAVES == 2 ? 2 : 1) void k_step(
         asm volatile("" : "+v"(o[0]), "+v"(o[17]), "+v"(sv[14]) : : "memory");
 #endif
         SBR_STAMP(12, false);                 // output values formed
-        store_rows2<OutT, SBR_NOBS, SBR_NSTATE>(obs + i0 * SBR_NOBS, state + i0 * SBR_NSTATE, l, stage, wide, o, sv);
+        store_rows2<OutT, SBR_NOBS, SBR_NSTATE, AGAIN>(obs + i0 * SBR_NOBS, state + i0 * SBR_NSTATE, l, stage, wide, o, sv);
     } else {
         if (obs) {
             OutT o[SBR_NOBS];

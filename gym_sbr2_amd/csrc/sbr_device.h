@@ -15,6 +15,14 @@
 #include "../../include/sbr_amd.h"
 
 #define SBR_DEV __device__ __forceinline__
+// A condition that only a rare call meets, as an `if` condition: with COLD (a constant expression) the branch carries the
+// "unlikely" weight and block placement moves its body out of the fall-through code; without, the bare condition - the compiler
+// folds the constant choice away before it forms the branch, so a build which does not ask for the layout keeps its text to the
+// byte (no cast, no negation around the bare form: either would turn a short-circuit `&&` into a computed value).
+// SBR_USUAL_IF: the other way round, for a condition only a rare call misses (its `else` is the cold body).
+// Must stand IN the `if`: the hint is lowered before inlining.
+#define SBR_RARE_IF(COLD, cond) ((COLD) ? (bool)__builtin_expect((long)(bool)(cond), 0L) : (cond))
+#define SBR_USUAL_IF(COLD, cond) ((COLD) ? !(bool)__builtin_expect((long)(bool)(!(cond)), 0L) : (cond))
 
 // ---------------------------------------------------------------------------------------------------
 // Wave-uniform model constants: sbr_config + everything that can be folded on the host (in fp64,
@@ -1054,7 +1062,9 @@ SBR_DEV double sbr_terminal(const SbrPar& p, SbrCtl& c, H& hs, double (&x)[SBR_N
 // TERMINAL_INLINE = false leaves the terminal phases of the done call to the caller (the fused rollout runs them once, after its
 // loop over the calls: with them inside the loop the compiler keeps their working set alive across it - 3 % of the rollout's
 // time, profiles/r03_notes.md); the reward of a done call does not depend on them unless OCI.
-template <bool OCI, int SCH, typename H, bool TERMINAL_INLINE = true, typename PK = SbrX6Reg>
+// COLD_END (k_step's one-wave scheme-1 builds): the end-of-episode branch is marked unlikely, so that block placement lays the
+// terminal phases behind the ordinary call's code instead of between its reward and its stores (profiles/r22_notes.md).
+template <bool OCI, int SCH, typename H, bool TERMINAL_INLINE = true, typename PK = SbrX6Reg, bool COLD_END = false>
 SBR_DEV double sbr_finish_step(const SbrPar& p, SbrCtl& c, H& hs, double (&x)[SBR_NX],
                                double (&xa6)[SBR_NXD], double& t_obs, bool& dn, double& qw, double& ksum, SbrRewardParts& rp,
                                const PK* pk = nullptr) {
@@ -1070,7 +1080,7 @@ SBR_DEV double sbr_finish_step(const SbrPar& p, SbrCtl& c, H& hs, double (&x)[SB
     }
     t_obs = c.t;
     dn = false;
-    if (c.t >= p.T5_end) {                                               // :1122
+    if (SBR_RARE_IF(COLD_END, c.t >= p.T5_end)) {                        // :1122
         dn = true;
         if ((TERMINAL_INLINE || OCI) && p.terminal) {
             const double snh_eff = x[10];            // solubles pass the settler unchanged: eff_component[3] (:2642)
