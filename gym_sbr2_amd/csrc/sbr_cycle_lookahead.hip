@@ -2,6 +2,8 @@
 //   k_cycle_lookahead   k_cycle over `fanout` candidate tapes of n_cycles whole cycles per env, each played from the env's current
 //              state and stored influent, nothing of the handle written (sbr_cycle_lookahead; the winners come from k_branch_best
 //              of sbr_tape.hip through launch_branch_best)
+//   cycle_lookahead_error   the one argument check of the three cycle lookaheads (this unit, sbr_cycle_scenarios.hip,
+//              sbr_cycle_models.hip); their kernel wrapper and reduce tail are sbr_host.h's
 #include "sbr_host.h"
 
 // The env's stored influent, addressed like its plant: (i0, l) = (first env of the workgroup, the lane's env minus it).
@@ -34,7 +36,7 @@ SBR_DEV void load_influent(const SbrBuf& b, int64_t i0, uint32_t l, double (&ld)
 //  * the row of cycle c + 1 is NOT fetched ahead of cycle c as the tape kernels fetch theirs: three or six more registers held
 //    through the cycle (five in the scheme-0 build, which put it above k_cycle's 225) to hide one load in front of some
 //    milliseconds.
-// The body is a device function and not the kernel because one build carries an attribute of its own (below); p and b by value,
+// The body is a device function and not the kernel because one build carries an attribute of its own (SBR_CYCLE_KERNEL); p and b by value,
 // as in sbr_lookahead_tape.
 template <typename ActT, int SCH>
 SBR_DEV void sbr_cycle_lookahead_branch(SbrPar p, SbrBuf b, int32_t n_cycles, uint32_t fanout, uint32_t n_branch,
@@ -86,45 +88,49 @@ SBR_DEV void sbr_cycle_lookahead_branch(SbrPar p, SbrBuf b, int32_t n_cycles, ui
     SbrPar p, SbrBuf b, int32_t n_cycles, uint32_t fanout, uint32_t n_branch, const ActT* __restrict__ actions,                  \
         double* __restrict__ returns, double* __restrict__ rewards_out, double* __restrict__ obs_end, double* __restrict__ diag_end, \
         uint8_t* __restrict__ status_out
-#define SBR_CYCLE_LOOKAHEAD_ARGS p, b, n_cycles, fanout, n_branch, actions, returns, rewards_out, obs_end, diag_end, status_out
-template <typename ActT, int SCH, int WAVES>
-__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_cycle_lookahead(SBR_CYCLE_LOOKAHEAD_PARAMS(ActT)) {
-    sbr_cycle_lookahead_branch<ActT, SCH>(SBR_CYCLE_LOOKAHEAD_ARGS);
+// the kernel, its two-waves specialisations and why they exist, and the assert on its first parameter: sbr_host.h
+SBR_CYCLE_KERNEL_PAR_FIRST(k_cycle_lookahead, sbr_cycle_lookahead_branch, SBR_CYCLE_LOOKAHEAD_PARAMS, p, b, n_cycles, fanout, n_branch,
+                           actions, returns, rewards_out, obs_end, diag_end, status_out)
+
+// What the three cycle lookaheads have to say about their arguments; empty if they are valid.  Every check is evaluated and the
+// LAST failing one is reported - all of them before anything is touched - so the order of this list is the precedence between
+// simultaneous faults, for all three: a NULL env last, a missing table just before it.  What varies between the entry points:
+//   n_scen         NULL where a branch is (env, candidate) and there are no futures (sbr_cycle_lookahead); max_scen its upper
+//                  bound, 0 for none (65535 where the futures are the grid's y axis: sbr_cycle_lookahead_models)
+//   need_influent  the futures' influent is the only one there is (sbr_cycle_lookahead_scenarios)
+//   need_table     the futures run under the handle's model table (sbr_cycle_lookahead_models)
+//   best_of_means  the winners are reduced from mean_out and not from returns (both entry points with futures)
+//   end_rows       obs_end, diag_end or status_out was asked for
+std::string cycle_lookahead_error(const sbr_env* e, int32_t n_cycles, int32_t fanout, const int32_t* n_scen, int32_t max_scen,
+                                  const void* actions, bool need_influent, const void* influent, bool need_table, const double* returns,
+                                  bool best_of_means, const double* mean_out, const double* worst_out, const int32_t* best_index,
+                                  const double* best_value, bool end_rows) {
+    std::string bad;
+    if (!best_of_means) best_error(bad, returns, best_index, best_value);
+    else if ((best_index || best_value) && !mean_out) bad = "best_index / best_value are reduced from mean_out: give mean_out with them";
+    if ((mean_out || worst_out) && !returns) bad = "mean_out / worst_out are reduced from returns: give returns with them";
+    if (n_cycles == 0 && end_rows) bad = "n_cycles = 0 has no last cycle for obs_end, diag_end or status_out";
+    if (need_influent && !influent && n_cycles > 0) bad = "NULL influent with n_cycles > 0";
+    if (!actions && n_cycles > 0) bad = "NULL actions with n_cycles > 0";
+    if (e && n_scen && fanout >= 1 && *n_scen >= 1 && e->n * (int64_t)fanout < (int64_t)1 << 31 &&
+        e->n * (int64_t)fanout * *n_scen >= (int64_t)1 << 31)
+        bad = "num_envs * fanout * n_scen must stay below 2^31 branches";
+    fanout_error(bad, e, fanout, nullptr);
+    if (n_scen && max_scen && *n_scen > max_scen) bad = "n_scen must be <= " + std::to_string(max_scen) + " (the futures are the grid's y axis)";
+    if (n_scen && *n_scen < 1) bad = "n_scen must be >= 1";
+    if (n_cycles < 0) bad = "n_cycles must be >= 0";
+    if (need_table && e && e->n_models < 1) bad = "no model table: call sbr_set_models first";
+    if (!e) bad = "NULL env";
+    return bad;
 }
-// The two-waves build of scheme 1, one explicit specialisation per tape type.  Two waves per SIMD leave a wave 256 registers;
-// this build, like k_cycle's, wants more and spills the rest to scratch.  How many of the 256 such a build ends up naming is
-// the allocator's business: an even count of ordinary registers plus those that hold spilled scalars in their lanes - 252 + 3
-// = 255 in k_cycle, 254 + 2 = 256 here, with fewer scalars spilled.  amdgpu_num_vgpr(127) asks for 2 x 127 = 254 of the unified
-// file (vector + accumulation registers): the build then takes 254 registers and 68 B of scratch per lane against k_cycle's 255
-// and 92 B (without the attribute: 256 registers), so that it needs no more than k_cycle of either.  An attribute takes no template
-// argument, hence specialisations and not a condition on WAVES.
-#define SBR_CYCLE_LOOKAHEAD_TWO_WAVES(ActT)                                                                                        \
-    template <>                                                                                                                    \
-    __global__ __launch_bounds__(SBR_BLOCK, 2) __attribute__((amdgpu_num_vgpr(127))) void k_cycle_lookahead<ActT, 1, 2>(           \
-        SBR_CYCLE_LOOKAHEAD_PARAMS(ActT)) {                                                                                        \
-        sbr_cycle_lookahead_branch<ActT, 1>(SBR_CYCLE_LOOKAHEAD_ARGS);                                                             \
-    }
-SBR_CYCLE_LOOKAHEAD_TWO_WAVES(float)
-SBR_CYCLE_LOOKAHEAD_TWO_WAVES(double)
-// The branch reads the constants a second time at offset 0 of the kernel-argument segment: every build - the specialisations are
-// written out by hand - takes SbrPar by value as its FIRST parameter.  (That the host fills it from e->par is launch_fused's.)
-#define SBR_TAKES_PAR_FIRST(...) std::is_same_v<SbrFirstParam<decltype(&k_cycle_lookahead<__VA_ARGS__>)>::type, SbrPar>
-static_assert(SBR_TAKES_PAR_FIRST(float, 1, 1) && SBR_TAKES_PAR_FIRST(double, 1, 1) && SBR_TAKES_PAR_FIRST(float, 1, 2) &&
-                  SBR_TAKES_PAR_FIRST(double, 1, 2) && SBR_TAKES_PAR_FIRST(float, 0, 2) && SBR_TAKES_PAR_FIRST(double, 0, 2),
-              "k_cycle_lookahead reads SbrPar at offset 0 of its kernel-argument segment");
 
 extern "C" {
 
 int sbr_cycle_lookahead(sbr_env* e, int32_t n_cycles, int32_t fanout, const void* actions, double* returns, double* rewards_out,
                         int32_t* best_index, double* best_return, double* obs_end, double* diag_end, uint8_t* status_out,
                         void* stream) {
-    std::string bad;                  // every check is evaluated, the LAST failing one is reported - before anything is touched
-    best_error(bad, returns, best_index, best_return);
-    if (n_cycles == 0 && (obs_end || diag_end || status_out)) bad = "n_cycles = 0 has no last cycle for obs_end, diag_end or status_out";
-    if (!actions && n_cycles > 0) bad = "NULL actions with n_cycles > 0";
-    fanout_error(bad, e, fanout, nullptr);
-    if (n_cycles < 0) bad = "n_cycles must be >= 0";
-    if (!e) bad = "NULL env";
+    const std::string bad = cycle_lookahead_error(e, n_cycles, fanout, nullptr, 0, actions, false, nullptr, false, returns, false, nullptr,
+                                                  nullptr, best_index, best_return, obs_end || diag_end || status_out);
     if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_cycle_lookahead: " + bad);
     const int64_t nb = e->n * (int64_t)fanout;
     return launched(e, [&] {

@@ -92,22 +92,10 @@ SBR_DEV void sbr_cycle_models_branch(const SbrPar* __restrict__ table, uint32_t 
     const SbrPar* __restrict__ table, uint32_t n_models, SbrBuf b, int32_t n_cycles, uint32_t fanout, uint32_t n_scen,           \
         uint32_t n_pairs, const ActT* __restrict__ actions, const double* __restrict__ influent, double* __restrict__ returns,   \
         double* __restrict__ rewards_out, double* __restrict__ obs_end, double* __restrict__ diag_end, uint8_t* __restrict__ status_out
-#define SBR_CYCLE_MODELS_ARGS \
-    table, n_models, b, n_cycles, fanout, n_scen, n_pairs, actions, influent, returns, rewards_out, obs_end, diag_end, status_out
-template <typename ActT, int SCH, int WAVES>
-__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_cycle_lookahead_models(SBR_CYCLE_MODELS_PARAMS(ActT)) {
-    sbr_cycle_models_branch<ActT, SCH>(SBR_CYCLE_MODELS_ARGS);
-}
-// The two-waves build of scheme 1 under the register cap of k_cycle_lookahead's (the comment there): one explicit specialisation
-// per tape type, since an attribute takes no template argument.
-#define SBR_CYCLE_MODELS_TWO_WAVES(ActT)                                                                                        \
-    template <>                                                                                                                 \
-    __global__ __launch_bounds__(SBR_BLOCK, 2) __attribute__((amdgpu_num_vgpr(127))) void k_cycle_lookahead_models<ActT, 1, 2>( \
-        SBR_CYCLE_MODELS_PARAMS(ActT)) {                                                                                        \
-        sbr_cycle_models_branch<ActT, 1>(SBR_CYCLE_MODELS_ARGS);                                                                \
-    }
-SBR_CYCLE_MODELS_TWO_WAVES(float)
-SBR_CYCLE_MODELS_TWO_WAVES(double)
+// the kernel and its two-waves specialisations: SBR_CYCLE_KERNEL (sbr_host.h).  The table comes first here and the constants are
+// read through it, so there is no first parameter to assert.
+SBR_CYCLE_KERNEL(k_cycle_lookahead_models, sbr_cycle_models_branch, SBR_CYCLE_MODELS_PARAMS, table, n_models, b, n_cycles, fanout, n_scen,
+                 n_pairs, actions, influent, returns, rewards_out, obs_end, diag_end, status_out)
 
 // ---------------------------------------------------------------------------------------------- which configs are models
 // sbr_config in declaration order, cut into the MODEL FIELDS - kinetics, stoichiometry, oxygen saturation: what a model of the
@@ -225,20 +213,8 @@ int sbr_cycle_lookahead_models(sbr_env* e, int32_t n_cycles, int32_t fanout, int
                                const double* influent, double* returns, double* rewards_out, double* mean_out, double* worst_out,
                                int32_t* best_index, double* best_value, double* obs_end, double* diag_end, uint8_t* status_out,
                                void* stream) {
-    std::string bad;                  // every check is evaluated, the LAST failing one is reported - before anything is touched
-    if ((best_index || best_value) && !mean_out) bad = "best_index / best_value are reduced from mean_out: give mean_out with them";
-    if ((mean_out || worst_out) && !returns) bad = "mean_out / worst_out are reduced from returns: give returns with them";
-    if (n_cycles == 0 && (obs_end || diag_end || status_out)) bad = "n_cycles = 0 has no last cycle for obs_end, diag_end or status_out";
-    if (!actions && n_cycles > 0) bad = "NULL actions with n_cycles > 0";
-    if (e && fanout >= 1 && n_scen >= 1 && e->n * (int64_t)fanout < (int64_t)1 << 31 &&
-        e->n * (int64_t)fanout * n_scen >= (int64_t)1 << 31)
-        bad = "num_envs * fanout * n_scen must stay below 2^31 branches";
-    fanout_error(bad, e, fanout, nullptr);
-    if (n_scen > 65535) bad = "n_scen must be <= 65535 (the futures are the grid's y axis)";
-    if (n_scen < 1) bad = "n_scen must be >= 1";
-    if (n_cycles < 0) bad = "n_cycles must be >= 0";
-    if (e && e->n_models < 1) bad = "no model table: call sbr_set_models first";
-    if (!e) bad = "NULL env";
+    const std::string bad = cycle_lookahead_error(e, n_cycles, fanout, &n_scen, 65535, actions, false, influent, true, returns, true, mean_out,
+                                                  worst_out, best_index, best_value, obs_end || diag_end || status_out);
     if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_cycle_lookahead_models: " + bad);
     const int64_t pairs = e->n * (int64_t)fanout;
     return launched(e, [&] {
@@ -249,8 +225,7 @@ int sbr_cycle_lookahead_models(sbr_env* e, int32_t n_cycles, int32_t fanout, int
                                         n_cycles, (uint32_t)fanout, (uint32_t)n_scen, (uint32_t)pairs, (const A*)actions, influent, returns,
                                         rewards_out, obs_end, diag_end, status_out);
         });
-        launch_scenario_stats(returns, pairs, n_scen, mean_out, worst_out, stream);
-        launch_branch_best(e, fanout, mean_out, best_index, best_value, stream);
+        launch_stats_and_best(e, fanout, n_scen, returns, mean_out, worst_out, best_index, best_value, stream);
     });
 }
 

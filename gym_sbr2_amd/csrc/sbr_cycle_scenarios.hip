@@ -83,29 +83,9 @@ SBR_DEV void sbr_cycle_scenarios_branch(SbrPar p, SbrBuf b, int32_t n_cycles, ui
     SbrPar p, SbrBuf b, int32_t n_cycles, uint32_t fanout, uint32_t n_scen, uint32_t n_branch, const ActT* __restrict__ actions, \
         const double* __restrict__ influent, double* __restrict__ returns, double* __restrict__ rewards_out,                     \
         double* __restrict__ obs_end, double* __restrict__ diag_end, uint8_t* __restrict__ status_out
-#define SBR_CYCLE_SCENARIOS_ARGS \
-    p, b, n_cycles, fanout, n_scen, n_branch, actions, influent, returns, rewards_out, obs_end, diag_end, status_out
-template <typename ActT, int SCH, int WAVES>
-__global__ __launch_bounds__(SBR_BLOCK, WAVES) void k_cycle_lookahead_scenarios(SBR_CYCLE_SCENARIOS_PARAMS(ActT)) {
-    sbr_cycle_scenarios_branch<ActT, SCH>(SBR_CYCLE_SCENARIOS_ARGS);
-}
-// The two-waves build of scheme 1 under the register cap of k_cycle_lookahead's (the comment there): one explicit specialisation
-// per tape type, since an attribute takes no template argument.
-#define SBR_CYCLE_SCENARIOS_TWO_WAVES(ActT)                                                                                        \
-    template <>                                                                                                                    \
-    __global__ __launch_bounds__(SBR_BLOCK, 2) __attribute__((amdgpu_num_vgpr(127))) void k_cycle_lookahead_scenarios<ActT, 1, 2>( \
-        SBR_CYCLE_SCENARIOS_PARAMS(ActT)) {                                                                                        \
-        sbr_cycle_scenarios_branch<ActT, 1>(SBR_CYCLE_SCENARIOS_ARGS);                                                             \
-    }
-SBR_CYCLE_SCENARIOS_TWO_WAVES(float)
-SBR_CYCLE_SCENARIOS_TWO_WAVES(double)
-// The branch reads the constants a second time at offset 0 of the kernel-argument segment (launch_fused fills it from e->par).
-#define SBR_SCENARIOS_TAKES_PAR_FIRST(...) \
-    std::is_same_v<SbrFirstParam<decltype(&k_cycle_lookahead_scenarios<__VA_ARGS__>)>::type, SbrPar>
-static_assert(SBR_SCENARIOS_TAKES_PAR_FIRST(float, 1, 1) && SBR_SCENARIOS_TAKES_PAR_FIRST(double, 1, 1) &&
-                  SBR_SCENARIOS_TAKES_PAR_FIRST(float, 1, 2) && SBR_SCENARIOS_TAKES_PAR_FIRST(double, 1, 2) &&
-                  SBR_SCENARIOS_TAKES_PAR_FIRST(float, 0, 2) && SBR_SCENARIOS_TAKES_PAR_FIRST(double, 0, 2),
-              "k_cycle_lookahead_scenarios reads SbrPar at offset 0 of its kernel-argument segment");
+// the kernel, its two-waves specialisations and the assert on its first parameter: SBR_CYCLE_KERNEL_PAR_FIRST (sbr_host.h)
+SBR_CYCLE_KERNEL_PAR_FIRST(k_cycle_lookahead_scenarios, sbr_cycle_scenarios_branch, SBR_CYCLE_SCENARIOS_PARAMS, p, b, n_cycles, fanout,
+                           n_scen, n_branch, actions, influent, returns, rewards_out, obs_end, diag_end, status_out)
 
 // Mean and worst case of each (env, candidate) pair's n_scen returns, behind the lookahead on the same stream: one lane per pair,
 // the futures walked in order.  mean = ((..(0.0 + r_0) + r_1 ..) + r_{S-1}) / S, one IEEE division, a NaN propagating through the
@@ -125,8 +105,8 @@ __global__ __launch_bounds__(SBR_BLOCK) void k_scenario_stats(const double* __re
     if (worst_out) worst_out[m] = worst;
 }
 
-// k_scenario_stats for the unit that shares it (sbr_cycle_models.hip): a kernel is named in one unit only.  Nothing is launched
-// when neither output was asked for.
+// k_scenario_stats for every caller, this unit's entry point and the other units' alike (launch_stats_and_best, sbr_host.h): a
+// kernel is named in one unit only.  Nothing is launched when neither output was asked for.
 void launch_scenario_stats(const double* returns, int64_t n_pairs, int32_t n_scen, double* mean_out, double* worst_out, void* stream) {
     if (mean_out || worst_out)
         hipLaunchKernelGGL(k_scenario_stats, grid_for(n_pairs), dim3(SBR_BLOCK), 0, (hipStream_t)stream, returns, n_pairs,
@@ -139,21 +119,10 @@ int sbr_cycle_lookahead_scenarios(sbr_env* e, int32_t n_cycles, int32_t fanout, 
                                   const double* influent, double* returns, double* rewards_out, double* mean_out, double* worst_out,
                                   int32_t* best_index, double* best_value, double* obs_end, double* diag_end, uint8_t* status_out,
                                   void* stream) {
-    std::string bad;                  // every check is evaluated, the LAST failing one is reported - before anything is touched
-    if ((best_index || best_value) && !mean_out) bad = "best_index / best_value are reduced from mean_out: give mean_out with them";
-    if ((mean_out || worst_out) && !returns) bad = "mean_out / worst_out are reduced from returns: give returns with them";
-    if (n_cycles == 0 && (obs_end || diag_end || status_out)) bad = "n_cycles = 0 has no last cycle for obs_end, diag_end or status_out";
-    if (!influent && n_cycles > 0) bad = "NULL influent with n_cycles > 0";
-    if (!actions && n_cycles > 0) bad = "NULL actions with n_cycles > 0";
-    if (e && fanout >= 1 && n_scen >= 1 && e->n * (int64_t)fanout < (int64_t)1 << 31 &&
-        e->n * (int64_t)fanout * n_scen >= (int64_t)1 << 31)
-        bad = "num_envs * fanout * n_scen must stay below 2^31 branches";
-    fanout_error(bad, e, fanout, nullptr);
-    if (n_scen < 1) bad = "n_scen must be >= 1";
-    if (n_cycles < 0) bad = "n_cycles must be >= 0";
-    if (!e) bad = "NULL env";
+    const std::string bad = cycle_lookahead_error(e, n_cycles, fanout, &n_scen, 0, actions, true, influent, false, returns, true, mean_out,
+                                                  worst_out, best_index, best_value, obs_end || diag_end || status_out);
     if (!bad.empty()) return fail(e, SBR_ERR_INVALID, "sbr_cycle_lookahead_scenarios: " + bad);
-    const int64_t pairs = e->n * (int64_t)fanout, nb = pairs * n_scen;
+    const int64_t nb = e->n * (int64_t)fanout * n_scen;
     return launched(e, [&] {
         dispatch(e, [&](auto c) {
             using C = decltype(c);
@@ -162,10 +131,7 @@ int sbr_cycle_lookahead_scenarios(sbr_env* e, int32_t n_cycles, int32_t fanout, 
                                  n_cycles, (uint32_t)fanout, (uint32_t)n_scen, (uint32_t)nb, (const A*)actions, influent, returns,
                                  rewards_out, obs_end, diag_end, status_out);
         });
-        if (mean_out || worst_out)
-            hipLaunchKernelGGL(k_scenario_stats, grid_for(pairs), dim3(SBR_BLOCK), 0, (hipStream_t)stream, returns, pairs,
-                               (uint32_t)n_scen, mean_out, worst_out);
-        launch_branch_best(e, fanout, mean_out, best_index, best_value, stream);
+        launch_stats_and_best(e, fanout, n_scen, returns, mean_out, worst_out, best_index, best_value, stream);
     });
 }
 

@@ -146,6 +146,39 @@ SBR_INTERNAL std::string models_error(const sbr_env* e, int64_t envs_per_model);
 template <typename F> struct SbrFirstParam;
 template <typename A, typename... R> struct SbrFirstParam<void (*)(A, R...)> { using type = A; };
 
+// The kernel around a cycle lookahead's branch body (sbr_cycle_lookahead.hip, sbr_cycle_scenarios.hip, sbr_cycle_models.hip):
+// K<ActT, SCH, WAVES> calls BRANCH<ActT, SCH>.  PARAMS(ActT) is the parameter list both share, the rest of the arguments its names.
+// The two-waves build of scheme 1 is an explicit specialisation per tape type.  Two waves per SIMD leave a wave 256 registers;
+// such a build, like k_cycle's, wants more and spills the rest to scratch.  How many of the 256 it ends up naming is the
+// allocator's business: an even count of ordinary registers plus those that hold spilled scalars in their lanes - 252 + 3 = 255 in
+// k_cycle, 254 + 2 = 256 in k_cycle_lookahead, with fewer scalars spilled.  amdgpu_num_vgpr(127) asks for 2 x 127 = 254 of the
+// unified file (vector + accumulation registers): k_cycle_lookahead then takes 254 registers and 68 B of scratch per lane against
+// k_cycle's 255 and 92 B (without the attribute: 256 registers), so that it needs no more than k_cycle of either.  An attribute
+// takes no template argument, hence specialisations and not a condition on WAVES.
+#define SBR_CYCLE_KERNEL(K, BRANCH, PARAMS, ...)                                                                              \
+    template <typename ActT, int SCH, int WAVES>                                                                              \
+    __global__ __launch_bounds__(SBR_BLOCK, WAVES) void K(PARAMS(ActT)) {                                                     \
+        BRANCH<ActT, SCH>(__VA_ARGS__);                                                                                       \
+    }                                                                                                                         \
+    template <>                                                                                                               \
+    __global__ __launch_bounds__(SBR_BLOCK, 2) __attribute__((amdgpu_num_vgpr(127))) void K<float, 1, 2>(PARAMS(float)) {     \
+        BRANCH<float, 1>(__VA_ARGS__);                                                                                        \
+    }                                                                                                                         \
+    template <>                                                                                                               \
+    __global__ __launch_bounds__(SBR_BLOCK, 2) __attribute__((amdgpu_num_vgpr(127))) void K<double, 1, 2>(PARAMS(double)) {   \
+        BRANCH<double, 1>(__VA_ARGS__);                                                                                       \
+    }
+// SBR_CYCLE_KERNEL for a branch that reads the constants a second time at offset 0 of the kernel-argument segment: every build -
+// the specialisations are written out on their own - takes SbrPar by value as its FIRST parameter.  (That the host fills it from
+// e->par is launch_fused's.)
+#define SBR_TAKES_PAR_FIRST(K, ...) std::is_same_v<SbrFirstParam<decltype(&K<__VA_ARGS__>)>::type, SbrPar>
+#define SBR_CYCLE_KERNEL_PAR_FIRST(K, BRANCH, PARAMS, ...)                                                   \
+    SBR_CYCLE_KERNEL(K, BRANCH, PARAMS, __VA_ARGS__)                                                         \
+    static_assert(SBR_TAKES_PAR_FIRST(K, float, 1, 1) && SBR_TAKES_PAR_FIRST(K, double, 1, 1) &&             \
+                      SBR_TAKES_PAR_FIRST(K, float, 1, 2) && SBR_TAKES_PAR_FIRST(K, double, 1, 2) &&         \
+                      SBR_TAKES_PAR_FIRST(K, float, 0, 2) && SBR_TAKES_PAR_FIRST(K, double, 0, 2),           \
+                  #K " reads SbrPar at offset 0 of its kernel-argument segment");
+
 // Argument checks that several families share, and the one kernel two of them launch without owning it: defined in
 // sbr_tape.hip, which owns k_branch_best.
 SBR_INTERNAL void fanout_error(std::string& bad, const sbr_env* e, int32_t fanout, const char* word);
@@ -160,6 +193,20 @@ SBR_INTERNAL std::string lookahead_error(const sbr_env* e, int32_t n_steps, int3
 SBR_INTERNAL std::string lookahead_sampled_error(const sbr_env* e, int32_t n_steps, int32_t hold, int32_t fanout, const void* nominal,
                                                  const sbr_sampler* sampler, const double* returns, const int32_t* best_index,
                                                  const double* best_return);
+// What sbr_cycle_lookahead, sbr_cycle_lookahead_scenarios and sbr_cycle_lookahead_models have to say about their arguments (empty
+// if they are valid): defined in sbr_cycle_lookahead.hip, which has the ordered list and what each argument switches.
+SBR_INTERNAL std::string cycle_lookahead_error(const sbr_env* e, int32_t n_cycles, int32_t fanout, const int32_t* n_scen,
+                                               int32_t max_scen, const void* actions, bool need_influent, const void* influent,
+                                               bool need_table, const double* returns, bool best_of_means, const double* mean_out,
+                                               const double* worst_out, const int32_t* best_index, const double* best_value,
+                                               bool end_rows);
 // k_scenario_stats for a caller outside its unit (sbr_cycle_scenarios.hip owns it): mean and worst of each pair's n_scen returns
 SBR_INTERNAL void launch_scenario_stats(const double* returns, int64_t n_pairs, int32_t n_scen, double* mean_out, double* worst_out,
                                         void* stream);
+// The reduce tail of a lookahead over futures, behind its kernel on the same stream: mean and worst of each pair's returns where
+// either was asked for, then the winners among an env's means where they were.
+static inline void launch_stats_and_best(const sbr_env* e, int32_t fanout, int32_t n_scen, const double* returns, double* mean_out,
+                                         double* worst_out, int32_t* best_index, double* best_value, void* stream) {
+    launch_scenario_stats(returns, e->n * (int64_t)fanout, n_scen, mean_out, worst_out, stream);
+    launch_branch_best(e, fanout, mean_out, best_index, best_value, stream);
+}

@@ -25,20 +25,46 @@ class CycleLookahead:
         return, NaN counting as -inf, ties to the lowest index); obs_end [N, K, 3] and diag_end [N, K, 12] float64, the
         observation and the diagnostics step() reports for the candidate's last cycle (at least one cycle then); status [N, K]
         uint8, the _capi.ST_* bits the candidate's state showed at the start or the end of any of its cycles."""
+        return CycleLookahead._cycle_fanout(self, "sbr_cycle_lookahead", candidates, None, None, return_rewards, False, return_best,
+                                            return_end, return_status, futures=False, one_cycle=True)
+
+    def _cycle_fanout(self, entry, candidates, influent, n_scen, return_rewards, return_stats, return_best, return_end, return_status,
+                      futures=True, one_cycle=False, need_influent=True):
+        """The front of the three lookaheads, `entry` the library's name of the one: the shape checks, n_scen, the 2^31 bound
+        before anything is sized by it, the inputs on the device and kept alive, the outputs through _fanout_outputs, the call.
+        What a method has at all: `futures`, a trailing axis of n_scen futures per candidate (influent, n_scen and return_stats
+        are theirs); `one_cycle`, the [N,K,3] shorthand; need_influent False, futures that may come without influent - n_scen is
+        then the caller's or num_models, and at most the 65535 rows of a grid's y axis.  Called through the class: the public
+        methods check their arguments on whatever `self` they are given."""
         shape = tuple(getattr(candidates, "shape", ()))
-        if len(shape) == 3:
+        if one_cycle and len(shape) == 3:
             shape = (1,) + shape
             candidates = candidates[None]
         if not (len(shape) == 4 and shape[1] == self.num_envs and shape[2] >= 1 and shape[3] == _capi.NCYC_ACT):
-            raise ValueError("candidates must have shape [n_cycles,N,K,3] or [N,K,3] with K >= 1")
+            raise ValueError("candidates must have shape [n_cycles,N,K,3]%s with K >= 1" % (" or [N,K,3]" if one_cycle else ""))
+        if futures and (need_influent or influent is not None):
+            ishape = tuple(getattr(influent, "shape", ()))
+            if not (len(ishape) == 4 and ishape[:2] == shape[:2] and ishape[2] >= 1 and ishape[3] == _capi.NX):
+                raise ValueError("influent must have shape [n_cycles,N,S,14] with S >= 1 and candidates' n_cycles")
+            if n_scen is not None and int(n_scen) != ishape[2]:
+                raise ValueError("n_scen must be influent's S when both are given")
+            n_scen = int(ishape[2])
+        elif futures:
+            n_scen = self.num_models if n_scen is None else int(n_scen)
+        if futures and not need_influent and not 1 <= n_scen <= 65535:
+            raise ValueError("n_scen must be in 1 .. 65535 (without influent and n_scen it is num_models: call set_models first)")
         n_cycles, fanout = int(shape[0]), int(shape[2])
-        if self.num_envs * fanout >= 2 ** 31:                    # before the outputs are sized by it
-            raise ValueError("num_envs * K must stay below 2^31")
-        a = self._keep_a = self._as_actions(candidates, shape)
+        if self.num_envs * fanout * (n_scen or 1) >= 2 ** 31:    # before the outputs are sized by it
+            raise ValueError("num_envs * K%s must stay below 2^31" % (" * S" if futures else ""))
+        a = self._as_actions(candidates, shape)
+        f = None if influent is None else self._dev(influent, torch.float64, ishape)
+        self._keep_a = (a, f)
         ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_cycles, 1, return_rewards, return_best,
-                                                       (return_end, return_end, return_status), end_rows=self._CYCLE_END_ROWS)
-        _capi.check(self.lib.sbr_cycle_lookahead(self._h, n_cycles, fanout, _ptr(a) if n_cycles else None, *ptrs, *end_ptrs,
-                                                 self._stream()), self._h)
+                                                       (return_end, return_end, return_status), end_rows=self._CYCLE_END_ROWS,
+                                                       n_scen=n_scen, return_stats=return_stats)
+        ins = [_ptr(t) if n_cycles else None for t in ((a, f) if futures else (a,))]
+        _capi.check(getattr(self.lib, entry)(self._h, n_cycles, fanout, *((n_scen,) if futures else ()), *ins, *ptrs, *end_ptrs,
+                                             self._stream()), self._h)
         return results
 
     def draw_influent(self, rows, per_env, seed=0, scenario=None, first_draw=0):
@@ -79,21 +105,8 @@ class CycleLookahead:
         [N, K], the mean over s (summed in s order, one division) and the smallest of a candidate's S returns, NaN if one of
         them is; best_index [N] int32 and best_value [N] float64, the winner among an env's means (cycle_lookahead's rule);
         obs_end [N, K, S, 3] and diag_end [N, K, S, 12] float64; status [N, K, S] uint8 - all as cycle_lookahead gives them."""
-        shape, ishape = tuple(getattr(candidates, "shape", ())), tuple(getattr(influent, "shape", ()))
-        if not (len(shape) == 4 and shape[1] == self.num_envs and shape[2] >= 1 and shape[3] == _capi.NCYC_ACT):
-            raise ValueError("candidates must have shape [n_cycles,N,K,3] with K >= 1")
-        if not (len(ishape) == 4 and ishape[:2] == shape[:2] and ishape[2] >= 1 and ishape[3] == _capi.NX):
-            raise ValueError("influent must have shape [n_cycles,N,S,14] with S >= 1 and candidates' n_cycles")
-        n_cycles, fanout, n_scen = int(shape[0]), int(shape[2]), int(ishape[2])
-        if self.num_envs * fanout * n_scen >= 2 ** 31:           # before the outputs are sized by it
-            raise ValueError("num_envs * K * S must stay below 2^31")
-        a, f = self._keep_a = (self._as_actions(candidates, shape), self._dev(influent, torch.float64, ishape))
-        ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_cycles, 1, return_rewards, return_best,
-                                                       (return_end, return_end, return_status), end_rows=self._CYCLE_END_ROWS,
-                                                       n_scen=n_scen, return_stats=return_stats)
-        _capi.check(self.lib.sbr_cycle_lookahead_scenarios(self._h, n_cycles, fanout, n_scen, _ptr(a) if n_cycles else None,
-                                                           _ptr(f) if n_cycles else None, *ptrs, *end_ptrs, self._stream()), self._h)
-        return results
+        return CycleLookahead._cycle_fanout(self, "sbr_cycle_lookahead_scenarios", candidates, influent, None, return_rewards,
+                                            return_stats, return_best, return_end, return_status)
 
     def set_models(self, models):
         """The handle's table of plant MODELS (sbr_set_models): `models` is a models.PlantModels or a sequence of _capi.SbrConfig
@@ -120,33 +133,8 @@ class CycleLookahead:
         both given they must agree.  At most 65535 futures.  The handle is left bit for bit as it was.  Results and their order
         are cycle_lookahead_scenarios': returns [N, K, S], then if asked for the rewards [n_cycles, N, K, S], mean and worst
         [N, K], best_index and best_value [N], obs_end [N, K, S, 3] and diag_end [N, K, S, 12], status [N, K, S]."""
-        shape = tuple(getattr(candidates, "shape", ()))
-        if not (len(shape) == 4 and shape[1] == self.num_envs and shape[2] >= 1 and shape[3] == _capi.NCYC_ACT):
-            raise ValueError("candidates must have shape [n_cycles,N,K,3] with K >= 1")
-        if influent is not None:
-            ishape = tuple(getattr(influent, "shape", ()))
-            if not (len(ishape) == 4 and ishape[:2] == shape[:2] and ishape[2] >= 1 and ishape[3] == _capi.NX):
-                raise ValueError("influent must have shape [n_cycles,N,S,14] with S >= 1 and candidates' n_cycles")
-            if n_scen is not None and int(n_scen) != ishape[2]:
-                raise ValueError("n_scen must be influent's S when both are given")
-            n_scen = int(ishape[2])
-        else:
-            n_scen = self.num_models if n_scen is None else int(n_scen)
-        if not 1 <= n_scen <= 65535:
-            raise ValueError("n_scen must be in 1 .. 65535 (without influent and n_scen it is num_models: call set_models first)")
-        n_cycles, fanout = int(shape[0]), int(shape[2])
-        if self.num_envs * fanout * n_scen >= 2 ** 31:           # before the outputs are sized by it
-            raise ValueError("num_envs * K * S must stay below 2^31")
-        a = self._as_actions(candidates, shape)
-        f = None if influent is None else self._dev(influent, torch.float64, ishape)
-        self._keep_a = (a, f)
-        ptrs, end_ptrs, results = self._fanout_outputs(fanout, n_cycles, 1, return_rewards, return_best,
-                                                       (return_end, return_end, return_status), end_rows=self._CYCLE_END_ROWS,
-                                                       n_scen=n_scen, return_stats=return_stats)
-        _capi.check(self.lib.sbr_cycle_lookahead_models(self._h, n_cycles, fanout, n_scen, _ptr(a) if n_cycles else None,
-                                                        _ptr(f) if n_cycles and f is not None else None, *ptrs, *end_ptrs,
-                                                        self._stream()), self._h)
-        return results
+        return CycleLookahead._cycle_fanout(self, "sbr_cycle_lookahead_models", candidates, influent, n_scen, return_rewards,
+                                            return_stats, return_best, return_end, return_status, need_influent=False)
 
 
 class SbrEnv2Vec(CycleLookahead, SbrOSVec):

@@ -2,7 +2,7 @@
 tests/test_lookahead_gpu.py, tests/test_lookahead_end_gpu.py, tests/test_mppi_gpu.py, tests/test_lookahead_policy_gpu.py; the plan
 rule: tests/test_gpu_parity.py, tests/test_plan_branches_gpu.py): the package behind their `G` fixtures, the seeded inputs, handles
 behind a non-default config, the check that no env left the model's domain, and what the fan-out tests build on - a live handle,
-seeded tapes and nets, the host's Philox and winner rule, torch.equal with NaN equal to NaN.  A plain module: pytest does not
+seeded tapes and nets, the host's Philox, winner rule and mean / worst rule, torch.equal with NaN equal to NaN.  A plain module: pytest does not
 rewrite its asserts, so each carries its message; torch is imported inside the helpers that need it."""
 import os
 
@@ -110,6 +110,18 @@ def host_best(v):
     r = v.cpu().numpy()
     idx = np.argmax(np.where(np.isnan(r), -np.inf, r), axis=1).astype(np.int32)
     return idx, r[np.arange(r.shape[0]), idx]
+
+
+def host_stats(ret):
+    """mean and worst of returns [N, K, S] as the header defines them: a float64 loop over s, then one division; the smallest,
+    NaN if any is NaN."""
+    r = ret.cpu().numpy()
+    acc = np.zeros(r.shape[:2])
+    for s in range(r.shape[2]):
+        acc = acc + r[:, :, s]
+    with np.errstate(invalid="ignore"):
+        worst = np.where(np.isnan(r).any(axis=2), np.nan, r.min(axis=2))
+    return acc / float(r.shape[2]), worst
 
 
 # Philox4x32-10 + Box-Muller in numpy (include/sbr_amd.h)

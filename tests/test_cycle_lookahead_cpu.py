@@ -2,17 +2,13 @@
 touched, the Python surface exists, the kernel lives in a translation unit of its own, and its gfx950 ISA (from the once-per-run
 cross-compile of tests/isa.py) needs no more registers and no more scratch than k_cycle's build of the same scheme and waves,
 with a store count bounded by its outputs.  The device-side refusals are in tests/test_cycle_lookahead_gpu.py."""
-import ctypes as C
 import inspect
-import os
-import re
 
 import pytest
-from conftest import ROOT
-from isa import kernel_names, library_asm, meta, unit_asms, vector_stores
+from cycle_kit import assert_declared_exported_and_bound, assert_null_env_refused, assert_unit_of_its_own, host_outputs
+from isa import library_asm, meta, vector_stores
 
 from gym_sbr2_amd import _capi
-from gym_sbr2_amd import build as B
 
 UNIT = "sbr_cycle_lookahead.hip"
 # (cfg.scheme, waves per SIMD) of the builds: scheme 0 has no one-wave build.  float32 tape, float32 outputs of k_cycle.
@@ -22,32 +18,15 @@ K_CYCLE = {b: "_Z7k_cycleIffLi%dELi%dEE" % b for b in BUILDS}
 
 
 def test_symbol_is_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "sbr_amd.h")) as f:
-        header = f.read()
-    assert re.search(r"^int sbr_cycle_lookahead\(sbr_env\* env, int32_t n_cycles, int32_t fanout, const void\* actions,", header, re.M)
-    assert "#define SBR_ABI_VERSION 6" in header
-    lib = _capi.load()
-    raw = C.CDLL(_capi.library_path())
-    assert getattr(raw, "sbr_cycle_lookahead") is not None
-    res, args = _capi.SYMBOLS["sbr_cycle_lookahead"]
-    fn = lib.sbr_cycle_lookahead
-    assert fn.restype is res and list(fn.argtypes) == args and len(args) == 12
-    assert lib.sbr_abi_version() == 6                  # an added function: no signature, struct or record width changed
+    assert_declared_exported_and_bound({"sbr_cycle_lookahead": (
+        r"^int sbr_cycle_lookahead\(sbr_env\* env, int32_t n_cycles, int32_t fanout, const void\* actions,", 12)})
 
 
 def test_null_env_is_refused_before_anything_is_touched():
-    lib = _capi.load()
-    tape = (C.c_float * 12)()
-    ret, rew, best = (C.c_double * 4)(*[7.0] * 4), (C.c_double * 4)(*[7.0] * 4), (C.c_double * 2)(*[7.0] * 2)
-    idx, st = (C.c_int32 * 2)(*[7] * 2), (C.c_uint8 * 4)(*[7] * 4)
-    obs, diag = (C.c_double * 12)(*[7.0] * 12), (C.c_double * 48)(*[7.0] * 48)
-    a, r, w, i, b, o, d, s = (C.cast(v, C.c_void_p) for v in (tape, ret, rew, idx, best, obs, diag, st))
-    # no handle can exist without a device; NULL env is the last check and names the entry point whatever else is wrong
-    for args in [(None, 1, 2, a, r, w, i, b, o, d, s, None), (None, -1, 0, None, None, w, i, b, o, d, s, None)]:
-        assert lib.sbr_cycle_lookahead(*args) == -1, args
-        assert lib.sbr_last_error(None) == b"sbr_cycle_lookahead: NULL env", lib.sbr_last_error(None)
-    assert list(ret) == [7.0] * 4 and list(rew) == [7.0] * 4 and list(best) == [7.0] * 2 and list(idx) == [7] * 2
-    assert list(obs) == [7.0] * 12 and list(diag) == [7.0] * 48 and list(st) == [7] * 4
+    bufs, p = host_outputs()
+    outs = tuple(p[name] for name in "rew idx best obs diag st".split())
+    assert_null_env_refused("sbr_cycle_lookahead", [(None, 1, 2, p["tape"], p["ret"]) + outs + (None,),
+                                                    (None, -1, 0, None, None) + outs + (None,)], bufs)
 
 
 def test_python_surface():
@@ -100,12 +79,8 @@ def test_setpoint_search_on_a_stand_in_env():
 
 
 def test_the_kernel_has_a_unit_of_its_own():
-    assert os.path.join(os.path.dirname(B.SRC), UNIT) in B.SOURCES
-    owners = {unit for unit, text in unit_asms().items() if any(n.startswith("_Z17k_cycle_lookahead") for n in kernel_names(text))}
-    assert owners == {UNIT}
-    want = sorted("_Z17k_cycle_lookaheadI%sLi%dELi%dEE" % ((t,) + b) for t in "fd" for b in BUILDS)      # float32 and float64 tapes
-    names = kernel_names(unit_asms()[UNIT])
-    assert sorted(n[:len(want[0])] for n in names) == want, names      # and no other kernel: k_branch_best stays sbr_tape.hip's
+    # the six builds, float32 and float64 tapes, and no other kernel: k_branch_best stays sbr_tape.hip's
+    assert_unit_of_its_own(UNIT, ["_Z17k_cycle_lookaheadI%sLi%dELi%dEE" % ((t,) + b) for t in "fd" for b in BUILDS])
 
 
 @pytest.fixture(scope="module")

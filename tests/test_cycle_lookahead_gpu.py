@@ -1,10 +1,10 @@
 """sbr_cycle_lookahead / SbrEnv2Vec.cycle_lookahead on the GPU: K tapes of whole cycles per env, each played from the live
 handle's current state and stored influent, the handle left bit for bit as it was.
 
-The checker of the bit-equality tests is the EXISTING per-cycle kernel on a second handle of N*K envs (`_replica`), driven
-through the existing API only: set_state with the live handle's get_state() columns repeated K times, reset(influent = the
-live handle's, repeated, carry_over=True), then per cycle step(candidates[c]) and between cycles the same reset again.  Both
-kernels inline the same device functions and the library is built with -ffp-contract=off, so everything is compared with ==
+The checker of the bit-equality tests is the EXISTING per-cycle kernel on a second handle of N*K envs (cycle_kit.replicas with
+the one future there is), driven through the existing API only: set_state with the live handle's get_state() columns repeated K
+times, reset(influent = the live handle's, repeated, carry_over=True), then per cycle step(candidates[c]) and between cycles the
+same reset again.  Both kernels inline the same device functions and the library is built with -ffp-contract=off, so everything is compared with ==
 under the stated dtype conversions.  The independent checker is the C oracle (oracle/sbr_oracle.py), with the tolerances of the
 float64 leg of tests/test_gpu_parity.py::test_cycle_env_sbr_v2_against_oracle_and_reference.
 
@@ -18,13 +18,13 @@ import ctypes as C
 
 import numpy as np
 import pytest
+from cycle_kit import BUILDS, IDS, assert_goes_on_like, assert_sentinels, assert_untouched, candidates as _candidates
+from cycle_kit import check_against_replicas, handle_bits, make_env as _env, replicas, sentinel_outputs, start
 from gpu_common import host_best, package, same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-BUILDS = [(0, False), (0, True), (1, False), (1, True)]          # (cfg.scheme, float64 outputs and actions)
-IDS = ["scheme%d-%s" % (s, "f64" if d else "f32") for s, d in BUILDS]
+EVERY = dict(return_rewards=True, return_best=True, return_end=True, return_status=True)
 
 
 @pytest.fixture(scope="module")
@@ -32,77 +32,14 @@ def G():
     return package()
 
 
-def _env(G, n, scheme=1, f64=False):
-    from gym_sbr2_amd import _capi
-    cfg = _capi.default_config(); cfg.scheme = scheme
-    dt = torch.float64 if f64 else torch.float32
-    env = G.SbrEnv2Vec(n, config=cfg, out_dtype=dt, action_dtype=dt)
-    assert env.cfg.scheme == scheme
-    return env
-
-
 def _start(G, n, scheme, f64, carried, seed):
     """A live handle on all eight scenarios: fresh from reset(rnd=...), or after a cycle, a carried-over reset and another cycle."""
-    rs = np.random.RandomState(seed)
-    scen = (np.arange(n) % 8).astype(np.int32)
-    env = _env(G, n, scheme, f64)
-    env.reset(scenario=scen, rnd=rs.randn(n, 48))
-    if carried:
-        env.step(torch.from_numpy(rs.uniform(0.1, 0.9, (n, 3))).cuda())
-        env.reset(scenario=scen, rnd=rs.randn(n, 48), carry_over=True)
-        env.step(torch.from_numpy(rs.uniform(0.1, 0.9, (n, 3))).cuda())
-    return env
-
-
-def _candidates(env, n_cycles, k, seed):
-    """[n_cycles, N, K, 3] ~ U(-0.2, 1.2) in the handle's action dtype: out-of-range values included (the kernel clips)."""
-    a = np.random.RandomState(seed).uniform(-0.2, 1.2, (n_cycles, env.num_envs, k, 3))
-    return torch.from_numpy(a).to(env.action_dtype).cuda()
-
-
-def _replica(G, env, cand, scheme, f64):
-    """Per cycle c: (reward [N, K] OutT, cobs [N, K, 3] OutT, diag [N, K, 12], the C_STATUS row [N, K] int64) of the per-cycle
-    kernel on a handle of N*K envs holding the live handle's state and influent K times."""
-    from gym_sbr2_amd import _capi
-    n_cycles, n, k = cand.shape[:3]
-    rep = _env(G, n * k, scheme, f64)
-    x, ctrl = env.get_state()
-    infl = env.influent().T.repeat_interleave(k, dim=0).contiguous()
-    rep.set_state(x.repeat_interleave(k, dim=1), ctrl.repeat_interleave(k, dim=1))
-    out = []
-    for c in range(n_cycles):
-        rep.reset(influent=infl, carry_over=True)
-        obs, rew, _ = rep.step(cand[c].reshape(n * k, 3))
-        out.append((rew.clone().reshape(n, k), obs.clone().reshape(n, k, 3), rep.diag.clone().reshape(n, k, _capi.NCYC_DIAG),
-                    rep.ctrl_row(_capi.C_STATUS).to(torch.int64).reshape(n, k)))
-    torch.cuda.synchronize()
-    rep.close()
-    return out
+    return start(G, n, scheme, f64, seed, carried=carried, stepped=True)
 
 
 def _check_against_replica(env, cand, rep):
     """Every output of cycle_lookahead(cand) against the replica's cycles `rep` (one entry per row of cand), with == on values."""
-    n_cycles = cand.shape[0]
-    ret, rew, bi, br, obs_end, diag_end, status = env.cycle_lookahead(cand, return_rewards=True, return_best=True, return_end=True,
-                                                                      return_status=True)
-    n, k = cand.shape[1:3]
-    assert ret.shape == (n, k) and ret.dtype == torch.float64 and rew.shape == (n_cycles, n, k) and rew.dtype == torch.float64
-    assert obs_end.shape == (n, k, 3) and diag_end.shape == (n, k, 12) and obs_end.dtype == diag_end.dtype == torch.float64
-    assert status.shape == (n, k) and status.dtype == torch.uint8
-    acc, st = torch.zeros_like(ret), torch.zeros_like(rep[0][3])
-    for c in range(n_cycles):
-        assert same(rew[c].to(env.out_dtype), rep[c][0]), "reward of cycle %d" % c
-        acc = acc + rew[c]
-        st |= rep[c][3]
-    assert same(ret, acc), "returns are the float64 sum of rewards_out in cycle order"
-    assert same(obs_end.to(env.out_dtype), rep[n_cycles - 1][1]) and same(diag_end, rep[n_cycles - 1][2])
-    assert torch.equal(status.to(torch.int64), st)
-    idx, val = host_best(ret)
-    assert np.array_equal(bi.cpu().numpy(), idx) and np.array_equal(br.cpu().numpy(), val, equal_nan=True)
-    assert bool((rew != 0).any())                                          # not a comparison of zeros
-    if n * k > 1:
-        assert len(torch.unique(ret)) > 1
-    return ret
+    return check_against_replicas(env, env.cycle_lookahead(cand, **EVERY), cand, None, rep)
 
 
 @pytest.mark.parametrize("carried", [False, True], ids=["fresh", "after-a-carried-cycle"])
@@ -110,28 +47,17 @@ def _check_against_replica(env, cand, rep):
 def test_same_bits_as_the_cycle_kernel_and_the_handle_is_untouched(G, scheme, f64, carried):
     """N = 300, K = 3: 900 branches - a partial last workgroup, and 256 % 3 != 0, so envs straddle workgroups.  Three cycles and
     one cycle against ONE replica run (its cycle 0 is the one-cycle launch's checker)."""
-    from gym_sbr2_amd import _capi
     n, k = 300, 3
     env, twin = _start(G, n, scheme, f64, carried, seed=31), _start(G, n, scheme, f64, carried, seed=31)
     cand = _candidates(env, 3, k, seed=32)
-    x0, c0 = env.get_state()
-    i0 = env.influent()
-    rep = _replica(G, env, cand, scheme, f64)
+    before = handle_bits(env)
+    rep = replicas(G, env, cand, f64=f64)
     _check_against_replica(env, cand, rep)
     _check_against_replica(env, cand[:1].contiguous(), rep[:1])
     # [N, K, 3] is one cycle
     assert same(env.cycle_lookahead(cand[0].contiguous()), env.cycle_lookahead(cand[:1].contiguous()))
-    x1, c1 = env.get_state()
-    assert torch.equal(x0, x1) and torch.equal(i0, env.influent())
-    for row in range(_capi.NCTRL):
-        assert same(c0[row], c1[row]), row
-    # the handle goes on as if nothing had happened: the next step() gives the bits of a twin that never looked ahead
-    act = _candidates(env, 1, 1, seed=33)[0, :, 0].contiguous()
-    obs_a, rew_a, _ = env.step(act)
-    obs_t, rew_t, _ = twin.step(act)
-    assert same(obs_a, obs_t) and same(rew_a, rew_t) and same(env.diag, twin.diag)
-    for u, v in zip(env.get_state(), twin.get_state()):
-        assert same(u, v)
+    assert_untouched(env, before)
+    assert_goes_on_like(env, twin, _candidates(env, 1, 1, seed=33)[0, :, 0].contiguous())
     env.close(); twin.close()
 
 
@@ -141,7 +67,7 @@ def test_addressing_edges(G, n, k):
     workgroup.  Two cycles each, against the replica."""
     env = _start(G, n, 1, False, False, seed=41)
     cand = _candidates(env, 2, k, seed=42)
-    _check_against_replica(env, cand, _replica(G, env, cand, 1, False))
+    _check_against_replica(env, cand, replicas(G, env, cand))
     env.close()
 
 
@@ -155,10 +81,9 @@ def test_two_waves_build_of_scheme_1(G, f64):
     env = _start(G, n, 1, f64, False, seed=45)
     assert n * k > env.query(_capi.Q_FUSED_ONE_WAVE_MAX_ENVS) >= n
     cand = _candidates(env, 2, k, seed=46)
-    x0, c0 = env.get_state()
-    _check_against_replica(env, cand, _replica(G, env, cand, 1, f64))
-    for u, v in zip((x0, c0), env.get_state()):
-        assert same(u, v)
+    before = handle_bits(env)
+    _check_against_replica(env, cand, replicas(G, env, cand, f64=f64))
+    assert_untouched(env, before)
     env.close()
 
 
@@ -232,11 +157,9 @@ def test_refusals_leave_the_outputs_alone(G):
     env = _start(G, n, 1, False, False, seed=81)
     lib, h = env.lib, env._h
     cand = _candidates(env, 1, k, seed=82)
-    outs = {name: torch.full(shape, 7, dtype=dt, device="cuda") for name, shape, dt in (
-        ("ret", (n * k,), torch.float64), ("rew", (n * k,), torch.float64), ("bi", (n,), torch.int32), ("br", (n,), torch.float64),
-        ("obs", (n * k, 3), torch.float64), ("diag", (n * k, 12), torch.float64), ("st", (n * k,), torch.uint8))}
-    p = {name: C.c_void_p(t.data_ptr()) for name, t in outs.items()}
+    outs, p = sentinel_outputs(n, k, 1)
     a = C.c_void_p(cand.data_ptr())
+    p["br"] = p["bv"]
     full = (p["ret"], p["rew"], p["bi"], p["br"], p["obs"], p["diag"], p["st"])
     refusals = [
         (h, -1, k, a) + full,                                                     # n_cycles < 0
@@ -252,9 +175,7 @@ def test_refusals_leave_the_outputs_alone(G):
     for args in refusals:
         assert lib.sbr_cycle_lookahead(*args, None) == -1, args[1:4]
         assert b"sbr_cycle_lookahead" in lib.sbr_last_error(h), args[1:4]
-    torch.cuda.synchronize()
-    for name, t in outs.items():
-        assert bool((t == 7).all()), name
+    assert_sentinels(outs)
     env.close()
 
 

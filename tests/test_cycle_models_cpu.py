@@ -7,17 +7,14 @@ than the outputs need and - the condition that shows the model block is read wit
 k_cycle_lookahead_scenarios plus the stored-influent path.  The device-side checks are in tests/test_cycle_models_gpu.py."""
 import ctypes as C
 import inspect
-import os
-import re
 import types
 
 import numpy as np
 import pytest
-from conftest import ROOT
-from isa import instructions, kernel_names, kernel_text, library_asm, meta, unit_asms, vector_stores
+from cycle_kit import assert_declared_exported_and_bound, assert_null_env_refused, assert_unit_of_its_own, host_outputs
+from isa import instructions, kernel_text, library_asm, meta, vector_stores
 
 from gym_sbr2_amd import _capi
-from gym_sbr2_amd import build as B
 
 UNIT = "sbr_cycle_models.hip"
 # (cfg.scheme, waves per SIMD) of the builds: scheme 0 has no one-wave build
@@ -29,54 +26,33 @@ ALL = sorted(K_MODELS)
 ALL_IDS = ["%s-scheme%d-%dwave" % (("f32" if t == "f" else "f64"), s, w) for t, s, w in ALL]
 
 MODEL_FIELDS = "Ya Yh fp ixb ixp muH Ks Koh Kno bH eta_g eta_h kh Kx muA Knh bA Koa ka So_sat".split()
-NEW = {"sbr_check_model": 2, "sbr_set_models": 3, "sbr_num_models": 1, "sbr_cycle_lookahead_models": 16}
 
 
 def test_symbols_are_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "sbr_amd.h")) as f:
-        header = f.read()
-    assert re.search(r"^int sbr_check_model\(const sbr_config\* base /\* NULL = defaults \*/, const sbr_config\* model\);", header, re.M)
-    assert re.search(r"^int sbr_set_models\(sbr_env\* env, int32_t n_models, const sbr_config\* models", header, re.M)
-    assert re.search(r"^int64_t sbr_num_models\(const sbr_env\* env\);", header, re.M)
-    assert re.search(r"^int sbr_cycle_lookahead_models\(sbr_env\* env, int32_t n_cycles, int32_t fanout, int32_t n_scen,", header, re.M)
-    assert "#define SBR_ABI_VERSION 6" in header
-    lib = _capi.load()
-    raw = C.CDLL(_capi.library_path())
-    for name, n_args in NEW.items():
-        assert getattr(raw, name) is not None
-        res, args = _capi.SYMBOLS[name]
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args and len(args) == n_args, name
+    assert_declared_exported_and_bound({
+        "sbr_check_model": (r"^int sbr_check_model\(const sbr_config\* base /\* NULL = defaults \*/, const sbr_config\* model\);", 2),
+        "sbr_set_models": (r"^int sbr_set_models\(sbr_env\* env, int32_t n_models, const sbr_config\* models", 3),
+        "sbr_num_models": (r"^int64_t sbr_num_models\(const sbr_env\* env\);", 1),
+        "sbr_cycle_lookahead_models": (
+            r"^int sbr_cycle_lookahead_models\(sbr_env\* env, int32_t n_cycles, int32_t fanout, int32_t n_scen,", 16)})
     assert _capi.SYMBOLS["sbr_num_models"][0] is C.c_int64
     assert _capi.SYMBOLS["sbr_cycle_lookahead_models"] == _capi.SYMBOLS["sbr_cycle_lookahead_scenarios"]
-    assert lib.sbr_abi_version() == 6                  # added functions: no signature, struct or record width changed
 
 
 def test_null_env_is_refused_before_anything_is_touched():
     lib = _capi.load()
-    tape, infl = (C.c_float * 12)(), (C.c_double * 28)()
-    bufs = {name: (ct * n)(*[7] * n) for name, ct, n in (
-        ("ret", C.c_double, 4), ("rew", C.c_double, 4), ("mean", C.c_double, 2), ("worst", C.c_double, 2), ("idx", C.c_int32, 1),
-        ("best", C.c_double, 1), ("obs", C.c_double, 12), ("diag", C.c_double, 48), ("st", C.c_uint8, 4))}
-    p = {name: C.cast(v, C.c_void_p) for name, v in bufs.items()}
-    a, f = C.cast(tape, C.c_void_p), C.cast(infl, C.c_void_p)
+    bufs, p = host_outputs()
     outs = tuple(p[name] for name in "ret rew mean worst idx best obs diag st".split())
-    # no handle can exist without a device; NULL env is the last check and names the entry point whatever else is wrong
-    for args in [(None, 1, 2, 2, a, f) + outs + (None,), (None, 1, 2, 2, a, None) + outs + (None,),
-                 (None, -1, 0, 70000, None, None, None) + outs[1:] + (None,)]:
-        assert lib.sbr_cycle_lookahead_models(*args) == -1, args
-        assert lib.sbr_last_error(None) == b"sbr_cycle_lookahead_models: NULL env", lib.sbr_last_error(None)
+    assert_null_env_refused("sbr_cycle_lookahead_models", [(None, 1, 2, 2, p["tape"], p["infl"]) + outs + (None,),
+                                                           (None, 1, 2, 2, p["tape"], None) + outs + (None,),
+                                                           (None, -1, 0, 70000, None, None, None) + outs[1:] + (None,)], bufs)
     models = (_capi.SbrConfig * 2)(_capi.default_config(), _capi.default_config())
     models[1].t_delta = 7.0                            # not looked at: there is no config to check it against
     before = bytes(models)
-    for args in [(None, 2, models), (None, -1, None), (None, 0, None)]:
-        assert lib.sbr_set_models(*args) == -1, args
-        assert lib.sbr_last_error(None) == b"sbr_set_models: NULL env", lib.sbr_last_error(None)
+    assert_null_env_refused("sbr_set_models", [(None, 2, models), (None, -1, None), (None, 0, None)], bufs)
     assert lib.sbr_num_models(None) == -1
     assert lib.sbr_last_error(None) == b"sbr_num_models: NULL env", lib.sbr_last_error(None)
     assert bytes(models) == before
-    for name, v in bufs.items():
-        assert list(v) == [7] * len(v), name
 
 
 # ---------------------------------------------------------------------------------------------- sbr_check_model
@@ -275,12 +251,7 @@ def test_robust_search_routes_to_the_models_call(risk):
 
 # ---------------------------------------------------------------------------------------------- the unit and its ISA
 def test_the_kernels_have_a_unit_of_their_own():
-    assert os.path.join(os.path.dirname(B.SRC), UNIT) in B.SOURCES
-    owners = {unit for unit, text in unit_asms().items() if any(n.startswith("_Z24k_cycle_lookahead_models") for n in kernel_names(text))}
-    assert owners == {UNIT}
-    names = sorted(kernel_names(unit_asms()[UNIT]))
-    want = sorted(K_MODELS.values())
-    assert len(names) == 6 and sorted(n[:len(want[0])] for n in names) == want, names       # the six builds, nothing else
+    assert_unit_of_its_own(UNIT, K_MODELS.values())                            # the six builds, nothing else
 
 
 @pytest.fixture(scope="module")

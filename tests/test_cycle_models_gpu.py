@@ -2,10 +2,10 @@
 RobustCycleSetpointSearch.plant_models): K candidate tapes per env, each played against S futures, future s under MODEL
 s % num_models of the handle's table, the handle left bit for bit as it was.
 
-The checker is the EXISTING per-cycle kernel, through the existing API only, as in tests/test_cycle_scenarios_gpu.py: per future s
-a second handle of N*K envs CREATED WITH THE CONFIG OF MODEL s % M (`_replicas`), given the live handle's state K times through
-get_state / set_state, then per cycle reset(influent = the future's rows expanded over k, carry_over=True) and
-step(candidates[c]).  Both kernels inline the same device functions and the library is built with -ffp-contract=off, so everything
+The checker is the EXISTING per-cycle kernel, through the existing API only, as in tests/test_cycle_scenarios_gpu.py: per model m
+a second handle CREATED WITH THE CONFIG OF MODEL m (cycle_kit.replicas) for the futures s with s % M = m, N*K envs for each of
+them, given the live handle's state through get_state / set_state, then per cycle reset(influent = the futures' rows expanded
+over k, carry_over=True) and step(candidates[c] expanded over those futures).  Both kernels inline the same device functions and the library is built with -ffp-contract=off, so everything
 is compared with == under the stated dtype conversions.  Where the models equal the handle's config the reference is
 cycle_lookahead / cycle_lookahead_scenarios itself.
 
@@ -15,43 +15,18 @@ import ctypes as C
 
 import numpy as np
 import pytest
-from gpu_common import host_best, package, same
+from cycle_kit import ALL, BUILDS, IDS, NAMES, assert_goes_on_like, assert_sentinels, assert_untouched as _assert_untouched
+from cycle_kit import candidates as _candidates, check_against_replicas, handle_bits as _handle_bits, replicas
+from cycle_kit import scen as _scen, sentinel_outputs, start as _start
+from gpu_common import package, same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-BUILDS = [(0, False), (0, True), (1, False), (1, True)]          # (cfg.scheme, float64 outputs and actions)
-IDS = ["scheme%d-%s" % (s, "f64" if d else "f32") for s, d in BUILDS]
-ALL = dict(return_rewards=True, return_stats=True, return_best=True, return_end=True, return_status=True)
-NAMES = "returns rewards mean worst best_index best_value obs_end diag_end status".split()
 
 
 @pytest.fixture(scope="module")
 def G():
     return package()
-
-
-def _env(G, n, cfg, f64=False):
-    from gym_sbr2_amd.models import copy_config
-    dt = torch.float64 if f64 else torch.float32
-    return G.SbrEnv2Vec(n, config=copy_config(cfg), out_dtype=dt, action_dtype=dt)
-
-
-def _scen(n):
-    return (np.arange(n) % 8).astype(np.int32)
-
-
-def _start(G, n, scheme=1, f64=False, seed=0):
-    """A live handle on all eight scenarios after a cycle and a carried-over reset: plant and stored influent are both its own."""
-    from gym_sbr2_amd import _capi
-    rs = np.random.RandomState(seed)
-    cfg = _capi.default_config(); cfg.scheme = scheme
-    env = _env(G, n, cfg, f64)
-    assert env.cfg.scheme == scheme
-    env.reset(scenario=_scen(n), rnd=rs.randn(n, 48))
-    env.step(torch.from_numpy(rs.uniform(0.1, 0.9, (n, 3))).cuda())
-    env.reset(scenario=_scen(n), rnd=rs.randn(n, 48), carry_over=True)
-    return env
 
 
 def _model(env, **factors):
@@ -66,85 +41,6 @@ def _model(env, **factors):
 def _two_models(env):
     """Model 0 the handle's own config; model 1 a slower nitrifier, a faster heterotroph and warmer water."""
     return [_model(env), _model(env, muA=0.7, muH=1.2, So_sat=0.95)]
-
-
-def _candidates(env, n_cycles, k, seed):
-    """[n_cycles, N, K, 3] ~ U(-0.2, 1.2) in the handle's action dtype: out-of-range values included (the kernel clips)."""
-    a = np.random.RandomState(seed).uniform(-0.2, 1.2, (n_cycles, env.num_envs, k, 3))
-    return torch.from_numpy(a).to(env.action_dtype).cuda()
-
-
-def _handle_bits(env):
-    x, c = env.get_state()
-    return x, c, env.influent()
-
-
-def _assert_untouched(env, before):
-    from gym_sbr2_amd import _capi
-    x, c, infl = _handle_bits(env)
-    assert torch.equal(before[0], x) and torch.equal(before[2], infl)
-    for row in range(_capi.NCTRL):
-        assert same(before[1][row], c[row]), row
-
-
-def _replicas(G, env, cand, infl, n_scen, models, f64):
-    """Per cycle c: (reward, cobs [.., 3], diag [.., 12], the C_STATUS row), every entry shaped [N, K, S, ..]: future s from a handle
-    of N*K envs created with models[s % M], holding the live handle's state K times, fed infl[c, :, s] - or, infl None, the live
-    handle's stored influent - and cand[c]."""
-    from gym_sbr2_amd import _capi
-    n_cycles, n, k = cand.shape[:3]
-    x, ctrl = env.get_state()
-    stored = env.influent().T.contiguous()
-    per_future = []
-    for s in range(n_scen):
-        rep = _env(G, n * k, models[s % len(models)], f64)
-        rep.set_state(x.repeat_interleave(k, dim=1), ctrl.repeat_interleave(k, dim=1))
-        cycles = []
-        for c in range(n_cycles):
-            rows = stored if infl is None else infl[c, :, s]
-            rep.reset(influent=rows.repeat_interleave(k, dim=0).contiguous(), carry_over=True)
-            obs, rew, _ = rep.step(cand[c].reshape(n * k, 3).contiguous())
-            cycles.append((rew.clone().reshape(n, k), obs.clone().reshape(n, k, 3), rep.diag.clone().reshape(n, k, _capi.NCYC_DIAG),
-                           rep.ctrl_row(_capi.C_STATUS).to(torch.int64).reshape(n, k)))
-        torch.cuda.synchronize()
-        rep.close()
-        per_future.append(cycles)
-    return [tuple(torch.stack([per_future[s][c][q] for s in range(n_scen)], dim=2) for q in range(4)) for c in range(n_cycles)]
-
-
-def _host_stats(ret):
-    """mean and worst of returns [N, K, S] as the header defines them: a float64 loop over s, then one division; the smallest,
-    NaN if any is NaN."""
-    r = ret.cpu().numpy()
-    acc = np.zeros(r.shape[:2])
-    for s in range(r.shape[2]):
-        acc = acc + r[:, :, s]
-    with np.errstate(invalid="ignore"):
-        worst = np.where(np.isnan(r).any(axis=2), np.nan, r.min(axis=2))
-    return acc / float(r.shape[2]), worst
-
-
-def _check_against_replicas(env, got, cand, s, rep):
-    """Every output of cycle_lookahead_models(cand, ..., **ALL) against the replicas' cycles `rep`, with == on values."""
-    n_cycles, (n, k) = cand.shape[0], cand.shape[1:3]
-    ret, rew, mean, worst, bi, bv, obs_end, diag_end, status = got
-    assert ret.shape == (n, k, s) and ret.dtype == torch.float64 and rew.shape == (n_cycles, n, k, s) and rew.dtype == torch.float64
-    assert mean.shape == worst.shape == (n, k) and mean.dtype == worst.dtype == torch.float64
-    assert obs_end.shape == (n, k, s, 3) and diag_end.shape == (n, k, s, 12) and obs_end.dtype == diag_end.dtype == torch.float64
-    assert status.shape == (n, k, s) and status.dtype == torch.uint8
-    acc, st = torch.zeros_like(ret), torch.zeros_like(rep[0][3])
-    for c in range(n_cycles):
-        assert same(rew[c].to(env.out_dtype), rep[c][0]), "reward of cycle %d" % c
-        acc = acc + rew[c]
-        st |= rep[c][3]
-    assert same(ret, acc), "returns are the float64 sum of rewards_out in cycle order"
-    assert same(obs_end.to(env.out_dtype), rep[n_cycles - 1][1]) and same(diag_end, rep[n_cycles - 1][2])
-    assert torch.equal(status.to(torch.int64), st)
-    hm, hw = _host_stats(ret)
-    assert np.array_equal(mean.cpu().numpy(), hm, equal_nan=True) and np.array_equal(worst.cpu().numpy(), hw, equal_nan=True)
-    idx, val = host_best(mean)
-    assert np.array_equal(bi.cpu().numpy(), idx) and np.array_equal(bv.cpu().numpy(), val, equal_nan=True)
-    assert bool((rew != 0).any()) and len(torch.unique(ret)) > 1           # not a comparison of zeros
 
 
 @pytest.mark.parametrize("scheme,f64", BUILDS, ids=IDS)
@@ -163,7 +59,7 @@ def test_same_bits_as_replicas_under_each_model(G, scheme, f64):
     before = _handle_bits(env)
     got = env.cycle_lookahead_models(cand, infl, **ALL)
     _assert_untouched(env, before)
-    _check_against_replicas(env, got, cand, s, _replicas(G, env, cand, infl, s, models, f64))
+    check_against_replicas(env, got, cand, s, replicas(G, env, cand, infl, s, models, f64))
     ret = got[0]
     # the same tape and influent under another plant: another return
     assert float((ret[..., 0] != ret[..., 1]).double().mean()) > 0.9
@@ -181,7 +77,7 @@ def test_stored_influent_under_two_models(G):
     before = _handle_bits(env)
     got = env.cycle_lookahead_models(cand, n_scen=s, **ALL)
     _assert_untouched(env, before)
-    _check_against_replicas(env, got, cand, s, _replicas(G, env, cand, None, s, models, False))
+    check_against_replicas(env, got, cand, s, replicas(G, env, cand, None, s, models))
     assert same(got[0][..., 0], got[0][..., 2].contiguous()) and not torch.equal(got[0][..., 0], got[0][..., 1])
     assert env.cycle_lookahead_models(cand).shape == (n, k, 2)             # n_scen defaults to num_models
     env.close()
@@ -260,16 +156,11 @@ def test_refusals_leave_the_outputs_and_the_table_alone(G):
     """Every refusal that needs a live handle: SBR_ERR_INVALID, the entry point named, sentinel-filled outputs unchanged."""
     from gym_sbr2_amd import _capi
     n, k, s = 4, 2, 3
-    b = n * k * s
     env = _start(G, n, seed=81)
     lib, h = env.lib, env._h
     cand = _candidates(env, 1, k, seed=82)
     infl = env.influent_futures(1, s)
-    outs = {name: torch.full(shape, 7, dtype=dt, device="cuda") for name, shape, dt in (
-        ("ret", (b,), torch.float64), ("rew", (b,), torch.float64), ("mean", (n * k,), torch.float64), ("worst", (n * k,), torch.float64),
-        ("bi", (n,), torch.int32), ("bv", (n,), torch.float64), ("obs", (b, 3), torch.float64), ("diag", (b, 12), torch.float64),
-        ("st", (b,), torch.uint8))}
-    p = {name: C.c_void_p(t.data_ptr()) for name, t in outs.items()}
+    outs, p = sentinel_outputs(n, k, s)
     a, f = C.c_void_p(cand.data_ptr()), C.c_void_p(infl.data_ptr())
     order = "ret rew mean worst bi bv obs diag st".split()
     full = tuple(p[name] for name in order)
@@ -312,9 +203,7 @@ def test_refusals_leave_the_outputs_and_the_table_alone(G):
         assert b"sbr_cycle_lookahead_models" in lib.sbr_last_error(h), args[1:4]
     assert lib.sbr_cycle_lookahead_models(h, 1, k, 65536, a, f, *full, None) == -1
     assert b"n_scen must be <= 65535" in lib.sbr_last_error(h)
-    torch.cuda.synchronize()
-    for name, t in outs.items():
-        assert bool((t == 7).all()), name
+    assert_sentinels(outs)
     assert env.num_models == 2
     env.close()
 
@@ -340,11 +229,7 @@ def test_replacing_and_dropping_the_table_and_every_other_call_unchanged(G):
         assert same(u, v), name
     act = _candidates(env, 1, 1, seed=93)[0, :, 0].contiguous()
     env.set_models(two)
-    obs_a, rew_a, _ = env.step(act)                                                # with a table
-    obs_t, rew_t, _ = twin.step(act)                                               # a twin that never had one
-    assert same(obs_a, obs_t) and same(rew_a, rew_t) and same(env.diag, twin.diag)
-    for u, v in zip(env.get_state(), twin.get_state()):
-        assert same(u, v)
+    assert_goes_on_like(env, twin, act)                                            # with a table, and a twin that never had one
     env.set_models(None)                                                           # dropped
     assert env.num_models == 0
     with pytest.raises(Exception, match="no model table"):
@@ -380,4 +265,72 @@ def test_robust_setpoint_search_over_plant_models(G, risk):
     else:
         assert not torch.equal(value, env.cycle_lookahead_scenarios(tape, search.futures, return_stats=True)[1][:, 0].contiguous())
     _assert_untouched(env, before)
+    env.close()
+
+
+def test_refusal_precedence_is_the_familys(G):
+    """Two or three faults at once, for each of the three entry points: the text is that of the LAST failing check in the family's
+    one ordered list - winners, mean / worst, n_cycles = 0 with end rows, NULL influent, NULL actions, the 2^31 bound with n_scen,
+    the fan-out, n_scen's upper and lower bound, n_cycles < 0, no table, NULL env - and nothing is written.  (N, K, S) = (3, 2, 2);
+    invalid arguments only, nothing is launched.  The texts were recorded from the three separate checks this list replaced."""
+    n, k, s = 3, 2, 2
+    env = _start(G, n, seed=85)
+    lib, h = env.lib, env._h
+    cand = _candidates(env, 1, k, seed=86)
+    infl = env.influent_futures(1, s)
+    outs, p = sentinel_outputs(n, k, s)
+    a, f = C.c_void_p(cand.data_ptr()), C.c_void_p(infl.data_ptr())
+
+    def refused(entry, want, handle=h, n_cycles=1, fanout=k, n_scen=s, actions=a, influent=f, drop=()):
+        futures = entry != "sbr_cycle_lookahead"
+        order = "ret rew mean worst bi bv obs diag st" if futures else "ret rew bi bv obs diag st"
+        args = (handle, n_cycles, fanout) + ((n_scen, actions, influent) if futures else (actions,))
+        args += tuple(None if name in drop else p[name] for name in order.split())
+        assert getattr(lib, entry)(*args, None) == -1, (entry, want)
+        got = lib.sbr_last_error(handle)
+        assert got == (entry + ": " + want).encode(), (entry, want, got)
+
+    END0 = "n_cycles = 0 has no last cycle for obs_end, diag_end or status_out"
+    NO_ACT, NO_INFL = "NULL actions with n_cycles > 0", "NULL influent with n_cycles > 0"
+    PAIRS, BRANCHES = "num_envs * fanout must stay below 2^31 branches", "num_envs * fanout * n_scen must stay below 2^31 branches"
+    FANOUT, SCEN, CYCLES = "fanout must be >= 1", "n_scen must be >= 1", "n_cycles must be >= 0"
+    STATS = "mean_out / worst_out are reduced from returns: give returns with them"
+    GRID = "n_scen must be <= 65535 (the futures are the grid's y axis)"
+    TABLE = "no model table: call sbr_set_models first"
+    one = "sbr_cycle_lookahead"
+    refused(one, END0, n_cycles=0, actions=None, drop=("ret", "rew"))                   # best_* without returns + end rows of no cycle
+    refused(one, NO_ACT, actions=None, drop=("ret",))                                   # best_* without returns + NULL actions
+    refused(one, FANOUT, n_cycles=0, actions=None, fanout=0, drop=("rew",))             # end rows of no cycle + fanout
+    refused(one, PAIRS, actions=None, fanout=2 ** 30)                                   # NULL actions + N * fanout >= 2^31
+    refused(one, CYCLES, n_cycles=-1, fanout=0, drop=("ret",))                          # best_*, fanout + n_cycles < 0
+    refused(one, "NULL env", handle=None, n_cycles=-1, fanout=0)                        # fanout, n_cycles < 0 + NULL env
+    for entry in ("sbr_cycle_lookahead_scenarios", "sbr_cycle_lookahead_models"):
+        models = entry.endswith("models")
+        if models:      # no table yet: it outranks everything but a NULL env
+            assert env.num_models == 0
+            refused(entry, TABLE, n_cycles=-1)                                        # n_cycles < 0 + no table
+            refused(entry, TABLE, n_scen=0, fanout=0, drop=("mean",))                   # winners, fanout, n_scen < 1 + no table
+            refused(entry, "NULL env", handle=None, n_cycles=-1)
+            env.set_models(_two_models(env))
+        refused(entry, STATS, drop=("ret", "mean"))                                     # winners without mean + worst without returns
+        refused(entry, END0, n_cycles=0, actions=None, influent=None, drop=("ret", "rew"))          # mean / worst + end rows of no cycle
+        if models:      # influent is optional here: its absence is no fault, and the check in front of it is reported
+            refused(entry, STATS, influent=None, drop=("ret",))
+            refused(entry, NO_ACT, actions=None, influent=None, drop=("ret",))          # mean / worst + NULL actions
+        else:
+            refused(entry, NO_INFL, influent=None, drop=("ret",))                       # mean / worst + NULL influent
+            refused(entry, NO_ACT, actions=None, influent=None)                         # NULL influent + NULL actions
+        refused(entry, BRANCHES, n_cycles=0, actions=None, influent=None, fanout=2 ** 15, n_scen=2 ** 15, drop=("rew",))      # end rows + 2^31
+        refused(entry, BRANCHES, actions=None, fanout=2 ** 15, n_scen=2 ** 15)          # NULL actions + the 2^31 bound with n_scen
+        refused(entry, FANOUT, actions=None, fanout=0)                                  # NULL actions + fanout
+        refused(entry, PAIRS, actions=None, fanout=2 ** 30, drop=("mean",))             # winners, NULL actions + N * fanout >= 2^31
+        if models:
+            refused(entry, GRID, fanout=2 ** 15, n_scen=2 ** 16)                        # the 2^31 bound with n_scen + the grid's y axis
+            refused(entry, GRID, fanout=0, n_scen=2 ** 16)                              # fanout + the grid's y axis
+            refused(entry, CYCLES, n_cycles=-1, n_scen=2 ** 16)                         # the grid's y axis + n_cycles < 0
+        refused(entry, SCEN, fanout=0, n_scen=0)                                        # fanout + n_scen < 1
+        refused(entry, CYCLES, n_cycles=-1, n_scen=0)                                   # n_scen < 1 + n_cycles < 0
+        refused(entry, CYCLES, n_cycles=-1, fanout=2 ** 15, n_scen=2 ** 15, drop=("ret",))          # mean / worst, 2^31 + n_cycles < 0
+        refused(entry, "NULL env", handle=None, n_cycles=-1, n_scen=0, fanout=0)        # three faults + NULL env
+    assert_sentinels(outs)
     env.close()

@@ -3,19 +3,15 @@ refuse a NULL handle before anything is touched, the Python surface exists, Robu
 does (on a stand-in env), the kernels live in a translation unit of their own, and their gfx950 ISA (from the once-per-run
 cross-compile of tests/isa.py) needs no more scratch than k_cycle's build of the same scheme and waves, with a store count bounded
 by the outputs.  The device-side checks are in tests/test_cycle_scenarios_gpu.py."""
-import ctypes as C
 import inspect
-import os
-import re
 import types
 
 import numpy as np
 import pytest
-from conftest import ROOT
+from cycle_kit import assert_declared_exported_and_bound, assert_null_env_refused, assert_unit_of_its_own, host_outputs
 from isa import kernel_names, library_asm, meta, unit_asms, vector_stores
 
 from gym_sbr2_amd import _capi
-from gym_sbr2_amd import build as B
 
 UNIT = "sbr_cycle_scenarios.hip"
 # (cfg.scheme, waves per SIMD) of the builds: scheme 0 has no one-wave build
@@ -28,39 +24,18 @@ ALL_IDS = ["%s-scheme%d-%dwave" % (("f32" if t == "f" else "f64"), s, w) for t, 
 
 
 def test_symbols_are_declared_exported_and_bound():
-    with open(os.path.join(ROOT, "include", "sbr_amd.h")) as f:
-        header = f.read()
-    assert re.search(r"^int sbr_draw_influent\(sbr_env\* env, uint64_t seed, int32_t rows, int32_t per_env, int32_t first_draw,", header, re.M)
-    assert re.search(r"^int sbr_cycle_lookahead_scenarios\(sbr_env\* env, int32_t n_cycles, int32_t fanout, int32_t n_scen,", header, re.M)
-    assert "#define SBR_ABI_VERSION 6" in header
-    lib = _capi.load()
-    raw = C.CDLL(_capi.library_path())
-    for name, n_args in (("sbr_draw_influent", 8), ("sbr_cycle_lookahead_scenarios", 16)):
-        assert getattr(raw, name) is not None
-        res, args = _capi.SYMBOLS[name]
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args and len(args) == n_args, name
-    assert lib.sbr_abi_version() == 6                  # added functions: no signature, struct or record width changed
+    assert_declared_exported_and_bound({
+        "sbr_draw_influent": (r"^int sbr_draw_influent\(sbr_env\* env, uint64_t seed, int32_t rows, int32_t per_env, int32_t first_draw,", 8),
+        "sbr_cycle_lookahead_scenarios": (
+            r"^int sbr_cycle_lookahead_scenarios\(sbr_env\* env, int32_t n_cycles, int32_t fanout, int32_t n_scen,", 16)})
 
 
 def test_null_env_is_refused_before_anything_is_touched():
-    lib = _capi.load()
-    tape, infl = (C.c_float * 12)(), (C.c_double * 28)()
-    bufs = {name: (ct * n)(*[7] * n) for name, ct, n in (
-        ("ret", C.c_double, 4), ("rew", C.c_double, 4), ("mean", C.c_double, 2), ("worst", C.c_double, 2), ("idx", C.c_int32, 1),
-        ("best", C.c_double, 1), ("obs", C.c_double, 12), ("diag", C.c_double, 48), ("st", C.c_uint8, 4), ("draws", C.c_double, 28))}
-    p = {name: C.cast(v, C.c_void_p) for name, v in bufs.items()}
-    a, f = C.cast(tape, C.c_void_p), C.cast(infl, C.c_void_p)
+    bufs, p = host_outputs()
     outs = tuple(p[name] for name in "ret rew mean worst idx best obs diag st".split())
-    # no handle can exist without a device; NULL env is the last check and names the entry point whatever else is wrong
-    for args in [(None, 1, 2, 2, a, f) + outs + (None,), (None, -1, 0, 0, None, None, None) + outs[1:] + (None,)]:
-        assert lib.sbr_cycle_lookahead_scenarios(*args) == -1, args
-        assert lib.sbr_last_error(None) == b"sbr_cycle_lookahead_scenarios: NULL env", lib.sbr_last_error(None)
-    for args in [(None, 0, 1, 2, 0, None, p["draws"], None), (None, 0, 0, 0, -1, None, None, None)]:
-        assert lib.sbr_draw_influent(*args) == -1, args
-        assert lib.sbr_last_error(None) == b"sbr_draw_influent: NULL env", lib.sbr_last_error(None)
-    for name, v in bufs.items():
-        assert list(v) == [7] * len(v), name
+    assert_null_env_refused("sbr_cycle_lookahead_scenarios", [(None, 1, 2, 2, p["tape"], p["infl"]) + outs + (None,),
+                                                              (None, -1, 0, 0, None, None, None) + outs[1:] + (None,)], bufs)
+    assert_null_env_refused("sbr_draw_influent", [(None, 0, 1, 2, 0, None, p["draws"], None), (None, 0, 0, 0, -1, None, None, None)], bufs)
 
 
 def test_python_surface():
@@ -146,15 +121,8 @@ def test_robust_setpoint_search_on_a_stand_in_env():
 
 
 def test_the_kernels_have_a_unit_of_their_own():
-    assert os.path.join(os.path.dirname(B.SRC), UNIT) in B.SOURCES
-    owners = {unit for unit, text in unit_asms().items()
-              if any(n.startswith(("_Z27k_cycle_lookahead_scenarios", K_STATS)) for n in kernel_names(text))}
-    assert owners == {UNIT}
-    names = sorted(kernel_names(unit_asms()[UNIT]))
-    want = sorted(K_SCEN.values())
-    stats = [n for n in names if n.startswith(K_STATS)]
-    assert len(stats) == 1 and len(names) == 7, names                  # the six lookahead builds, the mean / worst kernel, nothing else
-    assert sorted(n[:len(want[0])] for n in names if n not in stats) == want, names
+    # the six lookahead builds, the mean / worst kernel, nothing else
+    assert_unit_of_its_own(UNIT, K_SCEN.values(), others=(K_STATS,))
     assert any(n.startswith("_Z15k_draw_influent") for n in kernel_names(unit_asms()["sbr_core.hip"]))      # beside the resets
 
 

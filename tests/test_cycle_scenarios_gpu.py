@@ -2,7 +2,7 @@
 cycle_lookahead_scenarios, RobustCycleSetpointSearch): influent futures drawn without a reset, and K candidate tapes per env each
 played against the SAME S futures, the handle left bit for bit as it was.
 
-The checker of the bit-equality tests is the EXISTING per-cycle kernel on a second handle of B = N*K*S envs (`_replica`), driven
+The checker of the bit-equality tests is the EXISTING per-cycle kernel on a second handle of B = N*K*S envs (cycle_kit.replicas), driven
 through the existing API only, as in tests/test_cycle_lookahead_gpu.py: set_state with the live handle's get_state() columns
 repeated K*S times, then per cycle reset(influent = influent[c] expanded over k, carry_over=True) and step(candidates[c] expanded
 over s).  Both kernels inline the same device functions and the library is built with -ffp-contract=off, so everything is compared
@@ -15,13 +15,13 @@ import ctypes as C
 
 import numpy as np
 import pytest
+from cycle_kit import ALL, BUILDS, IDS, assert_goes_on_like, assert_sentinels, assert_untouched as _assert_untouched
+from cycle_kit import candidates as _candidates, check_against_replicas, handle_bits as _handle_bits, make_env as _env, replicas
+from cycle_kit import scen as _scen, sentinel_outputs, start as _start
 from gpu_common import host_best, normal_pair, package, same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-BUILDS = [(0, False), (0, True), (1, False), (1, True)]          # (cfg.scheme, float64 outputs and actions)
-IDS = ["scheme%d-%s" % (s, "f64" if d else "f32") for s, d in BUILDS]
 
 
 @pytest.fixture(scope="module")
@@ -29,105 +29,10 @@ def G():
     return package()
 
 
-def _env(G, n, scheme=1, f64=False, **kw):
-    from gym_sbr2_amd import _capi
-    cfg = _capi.default_config(); cfg.scheme = scheme
-    dt = torch.float64 if f64 else torch.float32
-    env = G.SbrEnv2Vec(n, config=cfg, out_dtype=dt, action_dtype=dt, **kw)
-    assert env.cfg.scheme == scheme
-    return env
-
-
-def _scen(n):
-    return (np.arange(n) % 8).astype(np.int32)
-
-
-def _start(G, n, scheme=1, f64=False, seed=0):
-    """A live handle on all eight scenarios after a cycle and a carried-over reset: plant and stored influent are both its own."""
-    rs = np.random.RandomState(seed)
-    env = _env(G, n, scheme, f64)
-    env.reset(scenario=_scen(n), rnd=rs.randn(n, 48))
-    env.step(torch.from_numpy(rs.uniform(0.1, 0.9, (n, 3))).cuda())
-    env.reset(scenario=_scen(n), rnd=rs.randn(n, 48), carry_over=True)
-    return env
-
-
-def _candidates(env, n_cycles, k, seed):
-    """[n_cycles, N, K, 3] ~ U(-0.2, 1.2) in the handle's action dtype: out-of-range values included (the kernel clips)."""
-    a = np.random.RandomState(seed).uniform(-0.2, 1.2, (n_cycles, env.num_envs, k, 3))
-    return torch.from_numpy(a).to(env.action_dtype).cuda()
-
-
-def _handle_bits(env):
-    x, c = env.get_state()
-    return x, c, env.influent()
-
-
-def _assert_untouched(env, before):
-    from gym_sbr2_amd import _capi
-    x, c, infl = _handle_bits(env)
-    assert torch.equal(before[0], x) and torch.equal(before[2], infl)
-    for row in range(_capi.NCTRL):
-        assert same(before[1][row], c[row]), row
-
-
-def _replica(G, env, cand, infl, scheme, f64):
-    """Per cycle c: (reward, cobs [.., 3], diag [.., 12], the C_STATUS row) of the per-cycle kernel on a handle of N*K*S envs
-    holding the live handle's state K*S times and fed infl[c] / cand[c] expanded over (k, s); every entry shaped [N, K, S, ..]."""
-    from gym_sbr2_amd import _capi
-    n_cycles, n, k = cand.shape[:3]
+def _check_against_replica(G, env, cand, infl, f64=False):
+    """Every output of cycle_lookahead_scenarios(cand, infl) against the per-cycle kernel under the same futures, with == on values."""
     s = infl.shape[2]
-    rep = _env(G, n * k * s, scheme, f64)
-    x, ctrl = env.get_state()
-    rep.set_state(x.repeat_interleave(k * s, dim=1), ctrl.repeat_interleave(k * s, dim=1))
-    out = []
-    for c in range(n_cycles):
-        rep.reset(influent=infl[c][:, None].expand(n, k, s, _capi.NX).reshape(n * k * s, _capi.NX).contiguous(), carry_over=True)
-        obs, rew, _ = rep.step(cand[c][:, :, None].expand(n, k, s, 3).reshape(n * k * s, 3).contiguous())
-        out.append((rew.clone().reshape(n, k, s), obs.clone().reshape(n, k, s, 3), rep.diag.clone().reshape(n, k, s, _capi.NCYC_DIAG),
-                    rep.ctrl_row(_capi.C_STATUS).to(torch.int64).reshape(n, k, s)))
-    torch.cuda.synchronize()
-    rep.close()
-    return out
-
-
-def _host_stats(ret):
-    """mean and worst of returns [N, K, S] as the header defines them: a float64 loop over s, then one division; the smallest,
-    NaN if any is NaN."""
-    r = ret.cpu().numpy()
-    acc = np.zeros(r.shape[:2])
-    for s in range(r.shape[2]):
-        acc = acc + r[:, :, s]
-    with np.errstate(invalid="ignore"):
-        worst = np.where(np.isnan(r).any(axis=2), np.nan, r.min(axis=2))
-    return acc / float(r.shape[2]), worst
-
-
-def _check_against_replica(env, cand, infl, rep):
-    """Every output of cycle_lookahead_scenarios(cand, infl) against the replica's cycles `rep`, with == on values."""
-    n_cycles, (n, k), s = cand.shape[0], cand.shape[1:3], infl.shape[2]
-    ret, rew, mean, worst, bi, bv, obs_end, diag_end, status = env.cycle_lookahead_scenarios(
-        cand, infl, return_rewards=True, return_stats=True, return_best=True, return_end=True, return_status=True)
-    assert ret.shape == (n, k, s) and ret.dtype == torch.float64 and rew.shape == (n_cycles, n, k, s) and rew.dtype == torch.float64
-    assert mean.shape == worst.shape == (n, k) and mean.dtype == worst.dtype == torch.float64
-    assert obs_end.shape == (n, k, s, 3) and diag_end.shape == (n, k, s, 12) and obs_end.dtype == diag_end.dtype == torch.float64
-    assert status.shape == (n, k, s) and status.dtype == torch.uint8
-    acc, st = torch.zeros_like(ret), torch.zeros_like(rep[0][3])
-    for c in range(n_cycles):
-        assert same(rew[c].to(env.out_dtype), rep[c][0]), "reward of cycle %d" % c
-        acc = acc + rew[c]
-        st |= rep[c][3]
-    assert same(ret, acc), "returns are the float64 sum of rewards_out in cycle order"
-    assert same(obs_end.to(env.out_dtype), rep[n_cycles - 1][1]) and same(diag_end, rep[n_cycles - 1][2])
-    assert torch.equal(status.to(torch.int64), st)
-    hm, hw = _host_stats(ret)
-    assert np.array_equal(mean.cpu().numpy(), hm, equal_nan=True) and np.array_equal(worst.cpu().numpy(), hw, equal_nan=True)
-    idx, val = host_best(mean)
-    assert np.array_equal(bi.cpu().numpy(), idx) and np.array_equal(bv.cpu().numpy(), val, equal_nan=True)
-    assert bool((rew != 0).any())                                          # not a comparison of zeros
-    if n * k * s > 1:
-        assert len(torch.unique(ret)) > 1
-    return ret
+    return check_against_replicas(env, env.cycle_lookahead_scenarios(cand, infl, **ALL), cand, s, replicas(G, env, cand, infl, s, f64=f64))
 
 
 # ---------------------------------------------------------------------------------------------- the draws
@@ -210,15 +115,9 @@ def test_same_bits_as_the_cycle_kernel_and_the_handle_is_untouched(G, scheme, f6
     cand = _candidates(env, 3, k, seed=32)
     infl = env.draw_influent(3, s, seed=9, scenario=_scen(n), first_draw=1)
     before = _handle_bits(env)
-    _check_against_replica(env, cand, infl, _replica(G, env, cand, infl, scheme, f64))
+    _check_against_replica(G, env, cand, infl, f64)
     _assert_untouched(env, before)
-    # the handle goes on as if nothing had happened: the next step() gives the bits of a twin that never looked ahead
-    act = _candidates(env, 1, 1, seed=33)[0, :, 0].contiguous()
-    obs_a, rew_a, _ = env.step(act)
-    obs_t, rew_t, _ = twin.step(act)
-    assert same(obs_a, obs_t) and same(rew_a, rew_t) and same(env.diag, twin.diag)
-    for u, v in zip(env.get_state(), twin.get_state()):
-        assert same(u, v)
+    assert_goes_on_like(env, twin, _candidates(env, 1, 1, seed=33)[0, :, 0].contiguous())
     env.close(); twin.close()
 
 
@@ -229,8 +128,7 @@ def test_one_future_equal_to_the_stored_influent_is_cycle_lookahead(G):
     infl = env.influent_futures(2, 1, seed=3)
     assert same(infl[0, :, 0], env.influent().T.contiguous()) and not torch.equal(infl[1], infl[0])
     infl[1] = infl[0]
-    got = env.cycle_lookahead_scenarios(cand, infl, return_rewards=True, return_stats=True, return_best=True, return_end=True,
-                                        return_status=True)
+    got = env.cycle_lookahead_scenarios(cand, infl, **ALL)
     ret, rew, bi, br, obs_end, diag_end, status = env.cycle_lookahead(cand, return_rewards=True, return_best=True, return_end=True,
                                                                       return_status=True)
     want = (ret[..., None], rew[..., None], ret, ret, bi, br, obs_end[:, :, None], diag_end[:, :, None], status[..., None])
@@ -258,7 +156,7 @@ def test_addressing_edges(G, n, k, s):
     env = _start(G, n, seed=51)
     cand = _candidates(env, 2, k, seed=52)
     infl = env.influent_futures(2, s, seed=6, scenario=_scen(n), first_draw=1)
-    _check_against_replica(env, cand, infl, _replica(G, env, cand, infl, 1, False))
+    _check_against_replica(G, env, cand, infl)
     env.close()
 
 
@@ -273,7 +171,7 @@ def test_two_waves_build_of_scheme_1(G, f64):
     cand = _candidates(env, 2, k, seed=56)
     infl = env.influent_futures(2, s, seed=7, scenario=_scen(n), first_draw=1)
     before = _handle_bits(env)
-    _check_against_replica(env, cand, infl, _replica(G, env, cand, infl, 1, f64))
+    _check_against_replica(G, env, cand, infl, f64)
     _assert_untouched(env, before)
     env.close()
 
@@ -296,16 +194,11 @@ def test_no_cycle_writes_zeros_and_touches_nothing(G):
 def test_refusals_leave_the_outputs_alone(G):
     """Every refusal that needs a live handle: SBR_ERR_INVALID, the entry point named, sentinel-filled outputs unchanged."""
     n, k, s = 4, 2, 3
-    b = n * k * s
     env = _start(G, n, seed=81)
     lib, h = env.lib, env._h
     cand = _candidates(env, 1, k, seed=82)
     infl = env.influent_futures(1, s)
-    outs = {name: torch.full(shape, 7, dtype=dt, device="cuda") for name, shape, dt in (
-        ("ret", (b,), torch.float64), ("rew", (b,), torch.float64), ("mean", (n * k,), torch.float64), ("worst", (n * k,), torch.float64),
-        ("bi", (n,), torch.int32), ("bv", (n,), torch.float64), ("obs", (b, 3), torch.float64), ("diag", (b, 12), torch.float64),
-        ("st", (b,), torch.uint8))}
-    p = {name: C.c_void_p(t.data_ptr()) for name, t in outs.items()}
+    outs, p = sentinel_outputs(n, k, s)
     a, f = C.c_void_p(cand.data_ptr()), C.c_void_p(infl.data_ptr())
     full = tuple(p[name] for name in "ret rew mean worst bi bv obs diag st".split())
 
@@ -331,9 +224,7 @@ def test_refusals_leave_the_outputs_alone(G):
     for args in refusals:
         assert lib.sbr_cycle_lookahead_scenarios(*args, None) == -1, args[1:4]
         assert b"sbr_cycle_lookahead_scenarios" in lib.sbr_last_error(h), args[1:4]
-    torch.cuda.synchronize()
-    for name, t in outs.items():
-        assert bool((t == 7).all()), name
+    assert_sentinels(outs)
     env.close()
 
 

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 import pytest
-from gpu_common import STEPS, host_best, live as _live, nominal as _nominal, package, same as _same, tape as _tape
+from gpu_common import STEPS, host_best, host_stats, live as _live, nominal as _nominal, package, same as _same, tape as _tape
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -64,18 +64,8 @@ def _unchanged(env, snap):
     return all(torch.equal(a, b) for a, b in zip(_snapshot(env), snap))
 
 
-def _host_stats(ret):
-    """The header's rule on the host: summed in m order, one division; the smallest return; NaN if one of them is."""
-    r = ret.cpu().numpy()
-    s = np.zeros(r.shape[:2])
-    for m in range(r.shape[2]):
-        s = s + r[:, :, m]
-    worst = np.where(np.isnan(r).any(axis=2), np.nan, r.min(axis=2))
-    return s / r.shape[2], worst
-
-
 def _check_stats(ret, mean, worst, bi, bv):
-    hm, hw = _host_stats(ret)
+    hm, hw = host_stats(ret)
     assert mean.shape == worst.shape == ret.shape[:2] and mean.dtype == worst.dtype == torch.float64
     assert np.array_equal(mean.cpu().numpy(), hm, equal_nan=True) and np.array_equal(worst.cpu().numpy(), hw, equal_nan=True)
     idx, val = host_best(mean)
